@@ -10,6 +10,17 @@ the start of each step).  `value` = B' pixels of all ranks / wall time of K time
   python bench.py [--gpus N --steps K --warmup W]           # N=1 default
   torchrun --nproc-per-node N bench.py --gpus N ...         # one process per GPU
 
+A plain run does what the headline needs and no more: set up, W warmup steps, the K timed steps,
+the result line (metric, value, unit, ms_per_step, dtype, config, stats).  --full adds everything
+else, each with runs of its own: the CPU baseline, the roofline figures (one extra single-stream
+pass when the timed steps ran concurrently), the parity self-check against a one-stream
+sequential run (exit 3 on a mismatch), cfg5's per-job digests and, at N > 1, the timed replicas
+reading (value_replicas).  --dump-outputs DIR writes what the last timed step returned to the
+host (B', s and im of every synthesised level, as fetched by the step's own D2H copy) as
+DIR/<name>.npy (B' float64, s and im float32: exact for these int32 values; at most 64 MB in all,
+a fixed seeded sample of each array when the whole would be larger) plus DIR/index.json.  The
+inputs are seeded, so two builds run with the same arguments can be compared array for array.
+
 Multi-GPU (N > 1): --mode shard (the default for cfg2/cfg3/cfg4: BASELINE config 3 as named)
 splits each pruned level's A database across the N ranks and steps N jobs sharing that A
 (synth.make_jobs: job 0 is the cfg job, the others other B images) through it together: every
@@ -22,10 +33,10 @@ rank scans its 1/N of the DB for the queries of all N jobs each wavefront step.
       (peer) or ncclAllGather + a finish kernel (rccl).
 Per-GPU scan work stays one job's ("weak"); --shard-jobs 1 with peer / rccl gives the one-job
 latency form ("strong").  The replicas aggregate (one independent job per GPU, no collective)
-rides along as value_replicas; --mode replicas makes that the value.
+rides along as value_replicas with --full; --mode replicas makes that the value.
 cfg5 splits its 64-job sweep job j -> rank j mod N (no collective).
 
-Besides the contract fields the JSON line carries:
+With --full the JSON line also carries:
   roofline     the dominant kernel (the certified pruned scan k3h_prune3: HBM roofline, algorithmic
                bytes / device time sampled live with HIP events every --time-stride-th wavefront
                step; traffic = PMC bytes per launch of the same config from profiles/), plus
@@ -345,11 +356,186 @@ def gather_rooflines(st):
     return out
 
 
+DUMP_BYTES = 64 * 1000 * 1000   # --dump-outputs: upper bound on the bytes of all arrays written
+
+
+def dump_outputs(path, names, arrays):
+    """--dump-outputs: arrays (the host buffers of the last timed step's D2H copy) -> path/<name>.npy,
+    float arrays as float64, int32 arrays (s, im: coordinates and image indices below 2^24) as float32.
+    Beyond DUMP_BYTES in all, every array is written as the same fraction of its flattened elements,
+    drawn without replacement by RandomState(seed 0) and sorted, so the sample depends on the array
+    sizes alone; path/index.json lists name, shape, dtype and the sample size of each."""
+    os.makedirs(path, exist_ok=True)
+    conv = [np.float64 if a.dtype.kind == 'f' else np.float32 for a in arrays]
+    total = sum(a.size * np.dtype(c).itemsize for a, c in zip(arrays, conv))
+    frac = min(1.0, 0.98 * DUMP_BYTES / max(total, 1))   # (0.98: the .npy headers and the rounding up below)
+    rs = np.random.RandomState(0)
+    index = []
+    for name, a, c in zip(names, arrays, conv):
+        flat = np.asarray(a).reshape(-1)
+        entry = {'name': name, 'shape': list(a.shape), 'source_dtype': str(a.dtype), 'dtype': np.dtype(c).name,
+                 'sampled': None}
+        if frac < 1.0:
+            n = max(1, int(flat.size * frac))
+            idx = np.sort(rs.choice(flat.size, n, replace=False))
+            x = flat[idx].astype(c)
+            entry['sampled'] = {'elements': n, 'of': int(flat.size), 'seed': 0,
+                                'rule': 'sorted RandomState(0).choice(size, n, replace=False), arrays in index order'}
+        else:
+            x = a.astype(c)
+        np.save(os.path.join(path, name + '.npy'), x)
+        index.append(entry)
+    with open(os.path.join(path, 'index.json'), 'w') as f:
+        json.dump({'arrays': index, 'max_bytes': DUMP_BYTES}, f, indent=1)
+    log('[bench] wrote %d arrays (%.1f MB%s) to %s' % (len(index), total * frac / 1e6,
+                                                        '' if frac >= 1.0 else ', sampled', path))
+
+
+def roofline_figures(args, st, st_all, elapsed, traffic, f16, peak, issued, achieved, k3_ms_per_launch, job_flops, jobs,
+                     concurrent, n_ctx, job):
+    """--full: the line's `roofline` from the sampled launches' stats (st: the single-stream pass when
+    the timed steps ran concurrently, else the timed steps) and the timed steps' stamps (st_all);
+    job = the one-job configs' job (None for the cfg5 sweep)."""
+    if st['prune_launches_timed'] > 0:
+        # the dominant kernel is the pruned scan (k3h_prune3), and it streams the DB tiles it
+        # needs: its roofline is HBM.  achieved = algorithmic bytes (DB tiles loaded x 7 KiB +
+        # tile boxes + queries + records, DESIGN.md §4b) / device time of its timed launches
+        p_s = st['prune_ms_timed'] * 1e-3
+        p_bytes = st['prune_bytes_timed'] / st['prune_launches_timed']
+        p_gbs = st['prune_bytes_timed'] / p_s / 1e9
+        p_tf = st['prune_flops_timed'] / p_s / 1e12
+        roofline = {'bound': 'hbm', 'achieved': p_gbs, 'peak': HBM_PEAK / 1e9, 'unit': 'GB/s',
+                    'frac': p_gbs * 1e9 / HBM_PEAK, 'traffic': traffic,
+                    'algorithmic_bytes_per_launch': p_bytes,
+                    'kernel': ('k3h_prune3 (certified pruned scan: PCA-box need tests, hi x hi block filter, split-f16 '
+                               '3 x v_mfma_f32_32x32x16_f16, fused packed-index top-2)'),
+                    'k3_us_per_launch': st['prune_ms_timed'] * 1e3 / st['prune_launches_timed'],
+                    'k3_launches_sampled': st['prune_launches_timed'],
+                    'mfma_achieved_tflops': p_tf, 'mfma_peak_tflops': peak / 1e12,
+                    'mfma_frac': p_tf * 1e12 / peak, 'mfma_issue_frac': p_tf * 1e12 * issued / peak,
+                    'all_k3_mfma_tflops': achieved / 1e12,
+                    'k3_share_of_step': st['dist_ms'] * (st['dist_flops'] / max(st['dist_flops_timed'], 1)) /
+                    max(elapsed * 1e3, 1e-9)}
+    else:
+        roofline = {'bound': 'mfma', 'achieved': achieved / 1e12, 'peak': peak / 1e12, 'unit': 'TFLOP/s',
+                    'frac': achieved / peak, 'traffic': traffic,
+                    'mfma_issue_frac': achieved * issued / peak,
+                    'kernel': ('k3h_scan (3 x v_mfma_f32_32x32x16_f16 on hi/lo-split operands, fused packed-index top-2)'
+                               if f16 else 'k3_dist (v_mfma_f32_32x32x2_f32 distance scan + fused top-2)'),
+                    'k3_us_per_launch': k3_ms_per_launch * 1e3, 'k3_launches_sampled': st['dist_launches_timed'],
+                    'k3_share_of_step': st['dist_ms'] * (st['dist_flops'] / max(st['dist_flops_timed'], 1)) /
+                    max(elapsed * 1e3, 1e-9)}
+
+    # SURVEY §8(d)'s own roofline basis: the brute-force NN flops of the job (sum 2*D*N_A*N_B,
+    # nothing pruned) per second, against the fp32 MFMA dense peak.  The timed kernel does not
+    # do that work (certified pruning skips most (DB tile, query tile) pairs), so this is an
+    # "equivalent" rate and may exceed the peak; pairs_frac is the share actually contracted.
+    fp32_equiv = job_flops * args.steps * jobs / elapsed
+    roofline['note'] = ('headline = the HBM frac of the dominant kernel (the certified pruned scan streams the DB '
+                        'tiles it needs); SURVEY §8(d)\'s fp32-MFMA basis (brute-force 2*D*N_A*N_B flops vs the fp32 '
+                        'matrix peak) does not apply under certified pruning, which skips most of that work on '
+                        'purpose: fp32_mfma_equiv_* is a work-equivalent rate, not a utilisation'
+                        if st['prune_launches_timed'] > 0 else
+                        'distance scan on MFMA; flops are the algorithmic 2*D*N_A*M per launch')
+    if concurrent:
+        roofline['k3_share_of_step'] = None   # single-stream pass vs concurrent timed steps: not comparable
+        roofline['timing'] = ('K3/K2/K4 device times from one extra single-stream pass (the timed steps ran %s, '
+                              'whose HIP events would overlap)' % ('%d concurrent streams' % n_ctx if n_ctx > 1
+                                                                  else 'pipelined levels on %d streams' % args.pipe_ctx))
+    if args.fuse_gather and st['prune_launches_timed'] > 0:
+        roofline['fused_gather'] = ('the unsampled steps of a pruned level run K4 of step t and K2p of step t + 1 as one '
+                                    'launch (k_merge_gather, DESIGN.md §6c); the sampled steps keep separate K2 / K4 '
+                                    'launches, which the gather / merge timings in roofline.gathers measure')
+    if st_all['k3p_stamp_launches'] > 0:
+        # the timed steps' own launches (kernel-written s_memrealtime stamps, no events): every
+        # pruned-scan launch of every timed step, in the configuration that is timed (pipelined
+        # levels, concurrent streams)
+        k3t = st_all['k3p_stamp_ms'] * 1e-3
+        # algorithmic bytes count each DB tile of a launch at most once (VERDICT r5 item 4): a
+        # launch of several query blocks (cfg4's wide steps) streams its tiles once per block, and
+        # those repeats are priced as waste, not as work (streamed_bytes_per_launch_timed)
+        ub = st_all.get('k3p_bytes_unique_all') or st_all['k3p_bytes_all']
+        roofline['frac_timed'] = ub / k3t / HBM_PEAK
+        roofline['achieved_timed'] = ub / k3t / 1e9
+        roofline['k3_us_per_launch_timed'] = st_all['k3p_stamp_ms'] * 1e3 / st_all['k3p_stamp_launches']
+        roofline['k3_launches_timed'] = st_all['k3p_stamp_launches']
+        roofline['algorithmic_bytes_per_launch_timed'] = ub / st_all['k3p_stamp_launches']
+        roofline['streamed_bytes_per_launch_timed'] = st_all['k3p_bytes_all'] / st_all['k3p_stamp_launches']
+        if ub < st_all['k3p_bytes_all']:  # the sampled reading on the same basis
+            for k in ('achieved', 'frac', 'algorithmic_bytes_per_launch'):
+                if k in roofline:   # (absent without sampled timing, --time-stride 0)
+                    roofline[k] *= ub / st_all['k3p_bytes_all']
+        if roofline.get('traffic'):
+            roofline['traffic_over_algorithmic'] = roofline['traffic'] / roofline['algorithmic_bytes_per_launch_timed']
+        # the launch = its workgroups' start spread (dispatch, CUs held by concurrent kernels)
+        # + their mean duration + the imbalance tail
+        roofline['k3_wg_us_timed'] = st_all['k3p_stamp_wg_ms'] * 1e3 / st_all['k3p_stamp_launches']
+        roofline['k3_start_spread_us_timed'] = st_all['k3p_stamp_start_ms'] * 1e3 / st_all['k3p_stamp_launches']
+        if st_all['merge_stamp_launches'] > 0:
+            roofline['merge_us_per_launch_timed'] = st_all['merge_stamp_ms'] * 1e3 / st_all['merge_stamp_launches']
+            roofline['merge_launches_timed'] = st_all['merge_stamp_launches']
+        # the fused merge + gather (k_merge_gather) of the same level: a latency-bound chain of
+        # dependent memory rounds per query (one wave each), priced against HBM for scale only.
+        # Bytes per query (DESIGN.md §6f): the scan's records (20 B per chunk), the query row and
+        # its pruning record, the coherence neighbours' s / im, the fp64 rows of the 15 coherence
+        # candidates and the reranked MFMA candidates (+ their A' values), then the next query's
+        # 55 features, its 30 U' candidates' s / im / NN rows and <= 28 fp64 U' rows, and the
+        # writes (B', s, im, NN row, stats word, q64, fragments, pruning record, handoff slot)
+        if st_all['merge_stamp_launches'] > 0 and job is not None:
+            lvl_px = float(np.prod(job.B_pyr[job.L - 1].shape[:2]))
+            q_per_launch = lvl_px * args.steps * jobs / st_all['merge_stamp_launches']
+            rr = st_all['reranked'] / max(st_all['pixels'], 1)
+            nwg = 256
+            bq = nwg * 20 + 496 + 15 * 12 + (15 + rr) * 456 + 440 + 30 * 12 + 28 * 448 + 780
+            mus = roofline['merge_us_per_launch_timed']
+            roofline['merge'] = {
+                'kernel': 'k_merge_gather (fused K4 merge of step t + K2p gather of step t + 1, one wave per query)',
+                'bound': 'latency', 'queries_per_launch': q_per_launch, 'reranked_per_query': rr,
+                'algorithmic_bytes_per_launch': bq * q_per_launch,
+                'achieved_gbs': bq * q_per_launch / (mus * 1e-6) / 1e9,
+                'frac_of_hbm': bq * q_per_launch / (mus * 1e-6) / HBM_PEAK,
+                'dependent_memory_rounds': 3,
+                'rounds': ('(1) the scan records + query row + neighbours\' s / im, (2) the candidates\' fp64 rows '
+                           '(the next query\'s features, neighbours and U\' rows load beside it and during the '
+                           'merge\'s compute: option early_gather), (3) the row above\'s handoff slot; then the '
+                           'late feature and the pruning record from registers'),
+                'us_per_launch_timed': mus}
+        if st_all['stamp_gaps'] > 0:
+            roofline['chain_gap_us_timed'] = st_all['stamp_gap_ms'] * 1e3 / st_all['stamp_gaps']
+            if st_all.get('stamp_gaps_sm', 0) > 0 and st_all['stamp_gaps'] > st_all['stamp_gaps_sm']:
+                # the two boundaries of a step: scan end -> merge start, merge end -> next scan start
+                roofline['chain_gap_scan_merge_us_timed'] = st_all['stamp_gap_sm_ms'] * 1e3 / st_all['stamp_gaps_sm']
+                roofline['chain_gap_merge_scan_us_timed'] = ((st_all['stamp_gap_ms'] - st_all['stamp_gap_sm_ms']) * 1e3
+                                                             / (st_all['stamp_gaps'] - st_all['stamp_gaps_sm']))
+            roofline['chain_window_ms_timed'] = st_all['stamp_window_ms'] / args.steps
+        roofline['timing_timed'] = ('frac_timed / *_timed: every pruned-scan (and fused merge) launch of the %d timed '
+                                    'steps, device time = max(workgroup end) - min(workgroup start) from s_memrealtime '
+                                    'stamps the kernels write (include/ia.h option "stamps")' % args.steps)
+    roofline['gathers'] = gather_rooflines(st)
+    roofline['fp32_mfma_equiv_tflops'] = fp32_equiv / 1e12
+    roofline['fp32_mfma_equiv_frac'] = fp32_equiv / FP32_MFMA_PEAK
+    roofline['pairs_frac'] = st['dist_pairs'] / max(st['dist_pairs_full'], 1.)
+    if st['dist_pairs_corrected'] > 0:
+        # the hi x hi block filter: every box-needed pair runs the hi x hi product; only this share
+        # also runs the two correction products and the top-2 epilogue (mfma_* above count 3)
+        roofline['pairs_corrected_frac'] = st['dist_pairs_corrected'] / max(st['dist_pairs'], 1.)
+        roofline['tiles_passing_frac'] = st['dist_tiles_rows'] / max(st['dist_tiles'], 1.)
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline: the CPU baseline, the roofline figures, the parity '
+                         'self-check against a one-stream sequential run, cfg5\'s per-job digests, value_replicas at '
+                         'N > 1 (a plain run sets up, warms up, times --steps steps and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (B\', s, im of every '
+                         'synthesised level) as DIR/<name>.npy, at most 64 MB in all (a fixed seeded sample of each '
+                         'array beyond that), with DIR/index.json')
     ap.add_argument('--config', default='cfg3', help='synthetic workload (ia_amd.synth.CONFIGS): cfg3 (default), '
                     'cfg2, cfg4 (2048^2 B vs 1024^2 A, kappa 25) or cfg5 (64-job sweep)')
     ap.add_argument('--sequential', action='store_true',
@@ -530,7 +716,7 @@ def main():
             % (rank, args.shard_jobs, args.config, time.time() - t0, job.L, job.pixels, job.flops()))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # host reference loop, sampled in spawned workers BEFORE this process initialises the GPU
         t1 = time.time()
         cpu = (cpu_baseline_sweep(sw, args.cpu_seconds, args.cpu_procs) if sw is not None
@@ -686,17 +872,28 @@ def main():
     # pipelined levels (or several cfg5 streams): HIP events around one stream's K3 launches would
     # also time the other stream's kernels, so the roofline comes from one extra sequential pass
     concurrent = len(ctxs) > 1 or (args.pipeline and sw is None and (not owner or pipe_owner) and args.shard_jobs <= 1)
-    elapsed, stats = timed(args.steps, run, not concurrent, hc)
-    # N = 1 self-check: the last timed step's fetched B', s, im (every level)
-    # must equal, bit for bit, a one-stream sequential run of the same job - the roofline pass
+    # (the sampled HIP events serve the roofline alone: a plain run times its steps without them)
+    elapsed, stats = timed(args.steps, run, args.full and not concurrent, hc)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's fetched results, before any later run overwrites the host buffers
+        torch.cuda.synchronize()
+        if sw is not None:
+            names = ['job%02d_%s_l%d' % (j, n, l) for j in mine for l in range(1, sw.L[j]) for n in ('Bp', 's', 'im')]
+        else:
+            nj = len(dj.dj) if isinstance(dj, DeviceBatch) else 1
+            names = ['%s%s_l%d' % ('job%d_' % j if nj > 1 else '', n, l)
+                     for j in range(nj) for l in range(1, job.L) for n in ('Bp', 's', 'im')]
+        dump_outputs(args.dump_outputs, names, [h.numpy() for h in hc.host])
+    # --full, N = 1 self-check: the last timed step's fetched B', s, im (every
+    # level) must equal, bit for bit, a one-stream sequential run of the same job - the roofline pass
     # below when the timed steps ran concurrently (pipelined levels, several cfg5 streams), else
     # one extra run
     # (cfg5 at any N: the rank's own jobs, also one sha1 per job - job_digests in the line, gathered
     # over the ranks, so a 2-rank sweep can be compared job by job with a one-GPU run)
-    self_check = world == 1 or sw is not None
+    self_check = args.full and (world == 1 or sw is not None)
     h_timed = hc.digest() if self_check else None
     job_digests = None
-    if sw is not None:
+    if sw is not None and args.full:
         dg = dict(zip(mine, hc.digest_groups([3 * (sw.L[j] - 1) for j in mine])))
         if dist:
             allg = [None] * world
@@ -712,7 +909,7 @@ def main():
         hx = HostCopy(dj1.outputs(), torch)
         hx.fetch()
         h_shard = hx.digest()
-    if concurrent:
+    if concurrent and args.full:
         _, stats_rl = timed(1, lambda st: run(st, [ctx]), True)
     else:
         stats_rl = stats
@@ -737,7 +934,7 @@ def main():
         # (value_replicas; never `value`: BASELINE config 3 is the sharded job)
         hc1 = HostCopy(dj1.outputs(), torch)
         rctx = make_context(args, local)
-        if args.no_replicas_extra:
+        if args.no_replicas_extra or not args.full:
             dj1.run(rctx, torch, _native.Stats())
             hc1.fetch()
         else:
@@ -817,130 +1014,8 @@ def main():
     # MFMA flops the kernel issues per algorithmic flop: 3 f16 passes over 16*KS padded k
     # (split-f16) or 2*KH padded k (fp32); query-tile padding to 32 not included
     issued = 3.0 * 16 * {1: 4, 2: 7}.get(ch, 0) / D if f16 else (56 if ch == 1 else 112 if ch == 2 else 168) / D
-    if st['prune_launches_timed'] > 0:
-        # the dominant kernel is the pruned scan (k3h_prune3), and it streams the DB tiles it
-        # needs: its roofline is HBM.  achieved = algorithmic bytes (DB tiles loaded x 7 KiB +
-        # tile boxes + queries + records) / device time of its timed launches
-        p_s = st['prune_ms_timed'] * 1e-3
-        p_bytes = st['prune_bytes_timed'] / st['prune_launches_timed']
-        p_gbs = st['prune_bytes_timed'] / p_s / 1e9
-        p_tf = st['prune_flops_timed'] / p_s / 1e12
-        roofline = {'bound': 'hbm', 'achieved': p_gbs, 'peak': HBM_PEAK / 1e9, 'unit': 'GB/s',
-                    'frac': p_gbs * 1e9 / HBM_PEAK, 'traffic': traffic,
-                    'algorithmic_bytes_per_launch': p_bytes,
-                    'kernel': ('k3h_prune3 (certified pruned scan: PCA-box need tests, hi x hi block filter, split-f16 '
-                               '3 x v_mfma_f32_32x32x16_f16, fused packed-index top-2)'),
-                    'k3_us_per_launch': st['prune_ms_timed'] * 1e3 / st['prune_launches_timed'],
-                    'k3_launches_sampled': st['prune_launches_timed'],
-                    'mfma_achieved_tflops': p_tf, 'mfma_peak_tflops': peak / 1e12,
-                    'mfma_frac': p_tf * 1e12 / peak, 'mfma_issue_frac': p_tf * 1e12 * issued / peak,
-                    'all_k3_mfma_tflops': achieved / 1e12,
-                    'k3_share_of_step': st['dist_ms'] * (st['dist_flops'] / max(st['dist_flops_timed'], 1)) /
-                    max(elapsed * 1e3, 1e-9)}
-    else:
-        roofline = {'bound': 'mfma', 'achieved': achieved / 1e12, 'peak': peak / 1e12, 'unit': 'TFLOP/s',
-                    'frac': achieved / peak, 'traffic': traffic,
-                    'mfma_issue_frac': achieved * issued / peak,
-                    'kernel': ('k3h_scan (3 x v_mfma_f32_32x32x16_f16 on hi/lo-split operands, fused packed-index top-2)'
-                               if f16 else 'k3_dist (v_mfma_f32_32x32x2_f32 distance scan + fused top-2)'),
-                    'k3_us_per_launch': k3_ms_per_launch * 1e3, 'k3_launches_sampled': st['dist_launches_timed'],
-                    'k3_share_of_step': st['dist_ms'] * (st['dist_flops'] / max(st['dist_flops_timed'], 1)) /
-                    max(elapsed * 1e3, 1e-9)}
-
-    # SURVEY §8(d)'s own roofline basis: the brute-force NN flops of the job (sum 2*D*N_A*N_B,
-    # nothing pruned) per second, against the fp32 MFMA dense peak.  The timed kernel does not
-    # do that work (certified pruning skips most (DB tile, query tile) pairs), so this is an
-    # "equivalent" rate and may exceed the peak; pairs_frac is the share actually contracted.
-    fp32_equiv = job_flops * args.steps * jobs / elapsed
-    roofline['note'] = ('headline = the HBM frac of the dominant kernel (the certified pruned scan streams the DB '
-                        'tiles it needs); SURVEY §8(d)\'s fp32-MFMA basis (brute-force 2*D*N_A*N_B flops vs the fp32 '
-                        'matrix peak) does not apply under certified pruning, which skips most of that work on '
-                        'purpose: fp32_mfma_equiv_* is a work-equivalent rate, not a utilisation'
-                        if st['prune_launches_timed'] > 0 else
-                        'distance scan on MFMA; flops are the algorithmic 2*D*N_A*M per launch')
-    if concurrent:
-        roofline['k3_share_of_step'] = None   # single-stream pass vs concurrent timed steps: not comparable
-        roofline['timing'] = ('K3/K2/K4 device times from one extra single-stream pass (the timed steps ran %s, '
-                              'whose HIP events would overlap)' % ('%d concurrent streams' % len(ctxs) if len(ctxs) > 1
-                                                                  else 'pipelined levels on %d streams' % args.pipe_ctx))
-    if args.fuse_gather and st['prune_launches_timed'] > 0:
-        roofline['fused_gather'] = ('the unsampled steps of a pruned level run K4 of step t and K2p of step t + 1 as one '
-                                    'launch (k_merge_gather, DESIGN.md §6c); the sampled steps keep separate K2 / K4 '
-                                    'launches, which the gather / merge timings in roofline.gathers measure')
-    if st_all['k3p_stamp_launches'] > 0:
-        # the timed steps' own launches (kernel-written s_memrealtime stamps, no events): every
-        # pruned-scan launch of every timed step, in the configuration that is timed (pipelined
-        # levels, concurrent streams)
-        k3t = st_all['k3p_stamp_ms'] * 1e-3
-        # algorithmic bytes count each DB tile of a launch at most once: a
-        # launch of several query blocks (cfg4's wide steps) streams its tiles once per block, and
-        # those repeats are priced as waste, not as work (streamed_bytes_per_launch_timed)
-        ub = st_all.get('k3p_bytes_unique_all') or st_all['k3p_bytes_all']
-        roofline['frac_timed'] = ub / k3t / HBM_PEAK
-        roofline['achieved_timed'] = ub / k3t / 1e9
-        roofline['k3_us_per_launch_timed'] = st_all['k3p_stamp_ms'] * 1e3 / st_all['k3p_stamp_launches']
-        roofline['k3_launches_timed'] = st_all['k3p_stamp_launches']
-        roofline['algorithmic_bytes_per_launch_timed'] = ub / st_all['k3p_stamp_launches']
-        roofline['streamed_bytes_per_launch_timed'] = st_all['k3p_bytes_all'] / st_all['k3p_stamp_launches']
-        if ub < st_all['k3p_bytes_all']:  # the sampled reading on the same basis
-            for k in ('achieved', 'frac', 'algorithmic_bytes_per_launch'):
-                if k in roofline:   # (absent without sampled timing, --time-stride 0)
-                    roofline[k] *= ub / st_all['k3p_bytes_all']
-        if roofline.get('traffic'):
-            roofline['traffic_over_algorithmic'] = roofline['traffic'] / roofline['algorithmic_bytes_per_launch_timed']
-        # the launch = its workgroups' start spread (dispatch, CUs held by concurrent kernels)
-        # + their mean duration + the imbalance tail
-        roofline['k3_wg_us_timed'] = st_all['k3p_stamp_wg_ms'] * 1e3 / st_all['k3p_stamp_launches']
-        roofline['k3_start_spread_us_timed'] = st_all['k3p_stamp_start_ms'] * 1e3 / st_all['k3p_stamp_launches']
-        if st_all['merge_stamp_launches'] > 0:
-            roofline['merge_us_per_launch_timed'] = st_all['merge_stamp_ms'] * 1e3 / st_all['merge_stamp_launches']
-            roofline['merge_launches_timed'] = st_all['merge_stamp_launches']
-        # the fused merge + gather (k_merge_gather) of the same level: a latency-bound chain of
-        # dependent memory rounds per query (one wave each), priced against HBM for scale only.
-        # Bytes per query: the scan's records (20 B per chunk), the query row and
-        # its pruning record, the coherence neighbours' s / im, the fp64 rows of the 15 coherence
-        # candidates and the reranked MFMA candidates (+ their A' values), then the next query's
-        # 55 features, its 30 U' candidates' s / im / NN rows and <= 28 fp64 U' rows, and the
-        # writes (B', s, im, NN row, stats word, q64, fragments, pruning record, handoff slot)
-        if st_all['merge_stamp_launches'] > 0 and sw is None:
-            lvl_px = float(np.prod(job.B_pyr[job.L - 1].shape[:2]))
-            q_per_launch = lvl_px * args.steps * jobs / st_all['merge_stamp_launches']
-            rr = st_all['reranked'] / max(st_all['pixels'], 1)
-            nwg = 256
-            bq = nwg * 20 + 496 + 15 * 12 + (15 + rr) * 456 + 440 + 30 * 12 + 28 * 448 + 780
-            mus = roofline['merge_us_per_launch_timed']
-            roofline['merge'] = {
-                'kernel': 'k_merge_gather (fused K4 merge of step t + K2p gather of step t + 1, one wave per query)',
-                'bound': 'latency', 'queries_per_launch': q_per_launch, 'reranked_per_query': rr,
-                'algorithmic_bytes_per_launch': bq * q_per_launch,
-                'achieved_gbs': bq * q_per_launch / (mus * 1e-6) / 1e9,
-                'frac_of_hbm': bq * q_per_launch / (mus * 1e-6) / HBM_PEAK,
-                'dependent_memory_rounds': 3,
-                'rounds': ('(1) the scan records + query row + neighbours\' s / im, (2) the candidates\' fp64 rows '
-                           '(the next query\'s features, neighbours and U\' rows load beside it and during the '
-                           'merge\'s compute: option early_gather), (3) the row above\'s handoff slot; then the '
-                           'late feature and the pruning record from registers'),
-                'us_per_launch_timed': mus}
-        if st_all['stamp_gaps'] > 0:
-            roofline['chain_gap_us_timed'] = st_all['stamp_gap_ms'] * 1e3 / st_all['stamp_gaps']
-            if st_all.get('stamp_gaps_sm', 0) > 0 and st_all['stamp_gaps'] > st_all['stamp_gaps_sm']:
-                # the two boundaries of a step: scan end -> merge start, merge end -> next scan start
-                roofline['chain_gap_scan_merge_us_timed'] = st_all['stamp_gap_sm_ms'] * 1e3 / st_all['stamp_gaps_sm']
-                roofline['chain_gap_merge_scan_us_timed'] = ((st_all['stamp_gap_ms'] - st_all['stamp_gap_sm_ms']) * 1e3
-                                                             / (st_all['stamp_gaps'] - st_all['stamp_gaps_sm']))
-            roofline['chain_window_ms_timed'] = st_all['stamp_window_ms'] / args.steps
-        roofline['timing_timed'] = ('frac_timed / *_timed: every pruned-scan (and fused merge) launch of the %d timed '
-                                    'steps, device time = max(workgroup end) - min(workgroup start) from s_memrealtime '
-                                    'stamps the kernels write (include/ia.h option "stamps")' % args.steps)
-    roofline['gathers'] = gather_rooflines(st)
-    roofline['fp32_mfma_equiv_tflops'] = fp32_equiv / 1e12
-    roofline['fp32_mfma_equiv_frac'] = fp32_equiv / FP32_MFMA_PEAK
-    roofline['pairs_frac'] = st['dist_pairs'] / max(st['dist_pairs_full'], 1.)
-    if st['dist_pairs_corrected'] > 0:
-        # the hi x hi block filter: every box-needed pair runs the hi x hi product; only this share
-        # also runs the two correction products and the top-2 epilogue (mfma_* above count 3)
-        roofline['pairs_corrected_frac'] = st['dist_pairs_corrected'] / max(st['dist_pairs'], 1.)
-        roofline['tiles_passing_frac'] = st['dist_tiles_rows'] / max(st['dist_tiles'], 1.)
+    roofline = roofline_figures(args, st, st_all, elapsed, traffic, f16, peak, issued, achieved, k3_ms_per_launch,
+                                job_flops, jobs, concurrent, len(ctxs), job if sw is None else None) if args.full else None
     out = {'metric': METRIC, 'value': value, 'unit': "B' px/s", 'n_gpus': world, 'steps': args.steps,
            'warmup': args.warmup, 'ms_per_step': elapsed * 1e3 / args.steps, 'higher_is_better': True,
            'scaling': 'strong' if (sw is not None or (args.mode == 'shard' and jobs < max(world, args.shard_emulate)))
@@ -981,6 +1056,8 @@ def main():
                                         'synth_ms', 'bound_violations', 'kappa_ambiguous', 'f16_levels', 'pruned_levels',
                                         'dist_pairs', 'dist_pairs_full', 'dist_tiles', 'dist_tiles_full',
                                         'dist_pairs_corrected')}}
+    if roofline is None:   # a plain run: no sampled launches, no single-stream pass
+        del out['roofline']
     if sw is not None:
         out['config']['sweep'] = {'jobs': len(sw.jobs), 'batched': not args.sequential, 'max_batch': args.max_batch,
                                   'streams': args.streams,

@@ -80,7 +80,8 @@ def test_cfg5_sweep_two_ranks_equal_one_gpu(tmp_path):
     if mode is None:
         pytest.skip('needs 2 GPUs (or IA_TEST_SHARE_GPU=1 for the one-GPU rehearsal)')
     env = dict(os.environ)
-    common = ['--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-replicas-extra', '--config', 'cfg5']
+    # --full: parity and job_digests come from runs and hashes beside the timed steps
+    common = ['--full', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-replicas-extra', '--config', 'cfg5']
     one = _bench(['--gpus', '1'] + common, env)
     if mode == 'share':
         env.update(IA_BENCH_SHARE_GPU='1', IA_BENCH_BACKEND='gloo')

@@ -17,8 +17,8 @@ fin = [r for r in rows if 'k3h_prune' in r['Kernel_Name']]
 st = fin[-1][sk]
 mine = [r for r in rows if r[sk] == st]
 pr = [i for i, r in enumerate(mine) if 'k3h_prune' in r['Kernel_Name']]
-# the last finest-level instance that other streams overlap (a pipelined job; bench.py's
-# roofline pass at the end runs the levels on one stream)
+# the last finest-level instance that other streams overlap (a pipelined job; the roofline pass
+# at the end of a bench.py --full run puts the levels on one stream)
 other_end = max((r['e'] for r in rows if r[sk] != st and r[sk] != rows[0][sk]), default=0)
 k = len(pr) // T
 while k > 1 and mine[pr[(k - 1) * T]]['s'] > other_end:

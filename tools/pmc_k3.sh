@@ -6,7 +6,7 @@ set -o pipefail
 OUT=${1:-gpurun_out/pmc}; V=${2:-1}; RX=${3:-k3h_dist}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-BENCH="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --time-stride 0 --k3-variant $V"
+BENCH="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --time-stride 0 --k3-variant $V"
 pass() {  # name counters...
   local name=$1; shift
   timeout -s KILL 180 rocprofv3 --pmc "$@" --kernel-include-regex "$RX" --output-format csv \

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 pass() {  # name counters...
   local name=$1; shift
   timeout -s KILL 150 rocprofv3 --pmc "$@" --kernel-include-regex "$RX" --output-format csv \
-      -d "$OUT/$name" -o run -- python3 bench.py --config "$CFG" --steps 1 --warmup 0 --no-cpu-baseline --time-stride 0 $EXTRA \
+      -d "$OUT/$name" -o run -- python3 bench.py --full --config "$CFG" --steps 1 --warmup 0 --no-cpu-baseline --time-stride 0 $EXTRA \
       > "$OUT/$name.log" 2>&1 || { echo "pass $name failed rc=$?"; tail -5 "$OUT/$name.log"; return 1; }
 }
 pass fetch FETCH_SIZE &&

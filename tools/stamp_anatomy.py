@@ -1,5 +1,5 @@
 """Anatomy of the pruned level's launches from raw kernel stamps (IA_STAMP_DUMP=<file>, written by
-libia for every stamped level with the largest pruned DB: bench.py with --steps 1 gives two records,
+libia for every stamped level with the largest pruned DB: bench.py --full --steps 1 gives two records,
 the timed pipelined job and the single-stream roofline pass).
 
 Per K3p launch: workgroup start spread, mean / max workgroup duration, the tail (last end - the
