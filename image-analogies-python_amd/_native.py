@@ -199,6 +199,7 @@ class Context(object):
         if device is None:
             device = int(os.environ.get('LOCAL_RANK', 0))
         self._h = ctypes.c_void_p()
+        self._opts = {}
         check(lib().ia_init(device, ctypes.byref(self._h)), 'ia_init(%d)' % device)
         self.device = device
 
@@ -219,6 +220,12 @@ class Context(object):
 
     def set_option(self, name, value):
         check(lib().ia_set_option(self._h, name.encode(), int(value)), 'ia_set_option')
+        self._opts[name] = int(value)
+
+    def option(self, name, default=None):
+        """The value last set for option `name` on this context (the C ABI has no getter), or
+        `default` - the caller's statement of the library default - when it was never set."""
+        return self._opts.get(name, default)
 
     def gaussian_pyramid(self, img, n_reduce, weights7):
         """ia_gaussian_pyramid on a host array: the n_reduce successive pyramid_reduce levels of

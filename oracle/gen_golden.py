@@ -327,7 +327,7 @@ def big_cases(mods, names):
         # levels, slim fixture.  ~1.5-2.5 h of container CPU with GEN_GOLDEN_THREADS=6.
         'g512': lambda: run_case(mods, 'g512', smooth(512, 512, 2, 1), [filt(smooth(512, 512, 2, 1))],
                                  smooth(512, 512, 2, 2), seed=3, slim=True, n_levels=5),
-        # check of the slim writer and the level cap against e2e_g64 (not committed)
+        # check of the slim writer and the level cap against e2e_g64 (committed: tests/golden/e2e_g64slim.npz)
         'g64slim': lambda: run_case(mods, 'g64slim', smooth(64, 64, 2, 1), [filt(smooth(64, 64, 2, 1))],
                                     smooth(64, 64, 2, 2), seed=3, slim=True, n_levels=4),
     }

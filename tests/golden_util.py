@@ -31,6 +31,43 @@ def load_e2e(name):
     return d
 
 
+def check_debug_records(z, out, Bp, st, name=''):
+    """The assertions of tests/test_gpu_debug.py on one run of every level with debug records:
+    out[level] = (s, im, dbg), Bp = the synthesised pyramid, st = the run's Stats.  s, im and B' of
+    every level, every NN index ('app_ix'), every coherence pick ('coh', (-1, -1, 0) for "no
+    candidate") and every compute_distance value ('dist', d_app then d_coh) must equal the
+    reference's, bit for bit."""
+    assert st.bound_violations == 0 and st.kappa_ambiguous == 0
+    app, coh, dist = [], [], []
+    for level in range(1, z['L']):
+        s, im, dbg = out[level]
+        assert np.array_equal(s, z['s'][level]) and np.array_equal(im, z['im'][level])
+        assert np.array_equal(Bp[level], z['Bp_final'][level])
+        src, d = dbg['src'], dbg['dist']
+        a_h, a_w = z['A_pyr'][level].shape[:2]
+        h, w = z['B_pyr'][level].shape[:2]
+        app.extend((src[:, 2].astype(np.int64) * a_h + src[:, 0]) * a_w + src[:, 1])
+        for qi in range(1, h * w):
+            if src[qi, 5]:
+                nb = src[qi, 3] * w + src[qi, 4]
+                r, c = divmod(qi, w)
+                coh.append((s[nb, 0] + r - src[qi, 3], s[nb, 1] + c - src[qi, 4], im[nb]))
+                dist.extend(d[qi])
+            else:
+                assert src[qi, 3] == 0 and src[qi, 4] == 0 and d[qi, 0] == 0 and d[qi, 1] == 0
+                coh.append((-1, -1, 0))
+        assert src[0, 5] == 0   # the level's first pixel never consults coherence (:186-189)
+    assert np.array_equal(np.array(app), z['app_ix'])
+    assert np.array_equal(np.array(coh), z['coh'])
+    dist = np.array(dist)
+    assert dist.shape == z['dist'].shape
+    print('%s: %d of %d compute_distance values bit-identical' % (name, int((dist == z['dist']).sum()), dist.size))
+    assert np.array_equal(dist, z['dist'])
+
+
+# library defaults of include/ia.h (ia_set_option has no getter: tests restore these by name)
+PRUNE_MIN_ROWS_DEFAULT = 1 << 19
+
 # round 6: reference run at BASELINE config 2's shape (512^2, the finest 5 levels), the size at
 # which the product's default path prunes; 'slim' fixture (oracle/gen_golden.py run_case slim=True)
 SLIM_CASES = [c for c in ['g512', 'g64slim'] if os.path.exists(os.path.join(GOLDEN, 'e2e_%s.npz' % c))]

@@ -14,7 +14,7 @@ import pickle
 import numpy as np
 import pytest
 
-from golden_util import BIG_CASES, E2E_CASES, load_e2e
+from golden_util import BIG_CASES, E2E_CASES, check_debug_records, load_e2e
 
 pytestmark = pytest.mark.gpu
 
@@ -66,32 +66,7 @@ def test_debug_records_match_reference_calls(ctx, name, prune_all, variant):
     if st.pruned_levels > 0:  # the hi x hi block filter runs on pruned levels only
         assert 0 < st.dist_pairs_corrected <= st.dist_pairs
         assert 0 < st.dist_tiles_rows <= st.dist_tiles
-    assert st.bound_violations == 0 and st.kappa_ambiguous == 0
-    app, coh, dist = [], [], []
-    for level in range(1, z['L']):
-        s, im, dbg = out[level]
-        assert np.array_equal(s, z['s'][level]) and np.array_equal(im, z['im'][level])
-        assert np.array_equal(Bp[level], z['Bp_final'][level])
-        src, d = dbg['src'], dbg['dist']
-        a_h, a_w = z['A_pyr'][level].shape[:2]
-        h, w = z['B_pyr'][level].shape[:2]
-        app.extend((src[:, 2].astype(np.int64) * a_h + src[:, 0]) * a_w + src[:, 1])
-        for qi in range(1, h * w):
-            if src[qi, 5]:
-                nb = src[qi, 3] * w + src[qi, 4]
-                r, c = divmod(qi, w)
-                coh.append((s[nb, 0] + r - src[qi, 3], s[nb, 1] + c - src[qi, 4], im[nb]))
-                dist.extend(d[qi])
-            else:
-                assert src[qi, 3] == 0 and src[qi, 4] == 0 and d[qi, 0] == 0 and d[qi, 1] == 0
-                coh.append((-1, -1, 0))
-        assert src[0, 5] == 0   # the level's first pixel never consults coherence (:186-189)
-    assert np.array_equal(np.array(app), z['app_ix'])
-    assert np.array_equal(np.array(coh), z['coh'])
-    dist = np.array(dist)
-    assert dist.shape == z['dist'].shape
-    print('%s: %d of %d compute_distance values bit-identical' % (name, int((dist == z['dist']).sum()), dist.size))
-    assert np.array_equal(dist, z['dist'])
+    check_debug_records(z, out, Bp, st, name)   # (shared with tests/test_gpu_options.py)
 
 
 def test_main_debug_writes_reference_pickles(ctx, tmp_path):

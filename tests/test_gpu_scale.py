@@ -98,7 +98,9 @@ def test_teacher_forced_cfg2(ctx):
 def test_teacher_forced_1024_levels_5_to_9(ctx):
     """cfg3 (BASELINE metric config): the full 10-level 1024^2 job (pruned scan on the 1024^2
     level), sampled pixels teacher-forced on each of levels 5..9 (64^2 .. 1024^2): 200 on levels
-    5-7, 1,000 on the 512^2 level and 800 on the 1024^2 level (the two pruned-scan levels)."""
+    5-7, 1,000 on the 512^2 level and 800 on the 1024^2 level.  Under the library defaults only the
+    1024^2 level runs the pruned scan (asserted below: pruned_levels == 1); the 512^2 level's
+    262,144 DB rows are under prune_min_rows = 2^19, so its decisions are the unpruned scan's."""
     from ia_amd import synth
     job = synth.make_job(1024)
     Bp, S, IM, st = _run_job(ctx, job)
