@@ -122,9 +122,9 @@ struct ia_ctx {
   DevBuf jobs;              // device JobPtrs[n_jobs]
   DevBuf db, db64, mu, Rbits, q64, qn2, qf, rec, recT, win, allwin, counters, absmax;
   // certified pruned scan (option "prune"): per-level basis, sorted DB table, tile boxes
-  DevBuf pr_part, pr_cov, pr_basis, pr_proj, pr_keys, pr_rows, pr_tmp, pos2row, boxes, qinfo, pairs, ord;
-  DevBuf qs_order, qs_info, qs_frag, qs_tbox;
-  DevBuf tnorm;  // per DB tile of a pruned level: R_t >= max |a'| over its rows (k3p_variant 14/15)  // presorted queries of a step (k3p_variant 11, K2s)
+  DevBuf pr_part, pr_cov, pr_basis, pr_proj, pr_keys, pr_rows, pr_tmp, pos2row, boxes, qinfo, pairs;
+  DevBuf qs_order, qs_info, qs_frag, qs_tbox;  // presorted queries of a step (K2s, or the fused gathers' sort)
+  DevBuf tnorm;  // per DB tile of a pruned level: R_t >= max |a'| over its rows
   DevBuf py_in, py_tmp, py_sm, py_mm, py_out;  // GPU preprocessing (ia_gaussian_pyramid, ia_color_matrix)
   std::vector<double> basis_h;   // staging of the basis upload (lives until the copy ran)
   int64_t prune_min_rows = IA_PRUNE_MIN_ROWS;  // option "prune_min_rows": smallest DB that prunes
@@ -369,7 +369,7 @@ void ia_destroy(ia_ctx *c) {
   for (DevBuf *b : {&c->A, &c->Ac, &c->Ap, &c->Apc, &c->jobs, &c->db, &c->db64,
                     &c->mu, &c->Rbits, &c->q64, &c->qn2, &c->qf, &c->rec, &c->recT, &c->win, &c->allwin, &c->counters, &c->absmax,
                     &c->pr_part, &c->pr_cov, &c->pr_basis, &c->pr_proj, &c->pr_keys, &c->pr_rows, &c->pr_tmp, &c->pos2row,
-                    &c->boxes, &c->qinfo, &c->pairs, &c->ord, &c->qs_order, &c->qs_info, &c->qs_frag, &c->qs_tbox, &c->tnorm,
+                    &c->boxes, &c->qinfo, &c->pairs, &c->qs_order, &c->qs_info, &c->qs_frag, &c->qs_tbox, &c->tnorm,
                     &c->stamp_k3, &c->stamp_mg, &c->stamp_dur,
                     &c->py_in, &c->py_tmp, &c->py_sm, &c->py_mm, &c->py_out})
     b->release();
@@ -570,23 +570,6 @@ int ia_comm_init(ia_ctx *c, int rank, int world, const unsigned char id[128]) {
   std::memcpy(&uid, id, 128);
   NCCL_TRY(ncclCommInitRank(&c->comm, world, uid, rank));
   return IA_OK;
-}
-
-// owner o's K2s of an owner-computes step: its queries sorted into every rank's area (area(p))
-extern "C++" template <class AreaFn>
-static void ia_launch_query_sort_xo_owner(ia_ctx *c, const LevelGeo &g, const float4 *qinfo, const void *qf,
-                                          const StepDesc &sd, int owner, int QTs, unsigned seq, int W, AreaFn area) {
-  (void)g;
-  XOSort xs{};
-  xs.inv = c->xo_inv.as<int>();
-  xs.W = W;
-  for (int p = 0; p < xs.W; p++) xs.area[p] = area(p);
-  xs.q0 = 0;
-  xs.Mj = sd.M;
-  xs.tile0 = owner * QTs;
-  xs.QTs = QTs;
-  xs.seq = seq;
-  ia_launch_query_sort_xo(qinfo, qf, xs, c->st);
 }
 
 // fresh = true (ia_xchg_alloc, before the ranks swap handles): a reused buffer is zeroed too and
@@ -797,30 +780,51 @@ static int check_level_args(const ia_level_args *a) {
 
 int ia_synthesize_level(ia_ctx *c, const ia_level_args *a, ia_stats *stats) { return ia_synthesize_levels(c, a, 1, stats); }
 
-int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_stats *stats) {
-  if (!c || !args) return fail(IA_EINVAL, "ia_synthesize_level: NULL argument");
-  if (n_jobs < 1 || n_jobs > IA_MAX_JOBS)
-    return fail(IA_EINVAL, "ia_synthesize_levels: n_jobs must be 1.." + std::to_string(IA_MAX_JOBS));
+// device-side waits (handoffs, exchange flags) give up after 20 s of the 100 MHz s_memrealtime clock
+static constexpr long long IA_WAIT_TICKS = 2000000000LL;
+
+static inline int64_t tile_pad(int64_t n) { return (n + IA_TILE - 1) / IA_TILE * IA_TILE; }
+
+// ---- phase 1: the plan ----------------------------------------------------------------------
+struct Shard {
+  int t0, t1, nwg, tpw;  // storage tiles [t0, t1) of the level's DB, scan decomposition
+};
+
+// What a level call decides before it builds the DB.  plan_shards fills the geometry and how the
+// level is sharded and exchanged; plan_scan, once the matcher is known (one device read-back),
+// the scan's decomposition and buffer sizes.
+struct LevelPlan {
+  LevelGeo g;
+  int J = 1, DP = 0;                  // jobs of the batch; fp32 columns of a DB row
+  size_t nA = 0, nAc = 0, nB = 0, nBc = 0;  // doubles of an A / coarse A / B / coarse B image
+  int64_t NB = 0;                     // pixels of the B level
+  bool sharded = false, emulated = false, multi = false;
+  bool xchg = false;                  // peer-write winner exchange (k_merge_xchg)
+  bool xo = false;                    // owner-computes sharded steps (exchange = 2, ia_internal.h XOLayout)
+  int Wsh = 1;                        // shards of this level
+  // plan_scan
+  bool use_h = false, prune = false;  // split-f16 matcher; certified pruned scan
+  int64_t T = 0, Mmax = 0;            // wavefront steps, queries of the widest step of one job ...
+  int64_t Mtmax = 0, Mpad_max = 0;    // ... and over all jobs (padded to query tiles)
+  int xo_bpj = 1, xo_QTx = 1, xo_QTs = 1;  // owner geometry: per owner bpj blocks of QTx tiles, QTs = bpj QTx
+  int ns = 0;                         // DB tiles this process holds
+  std::vector<Shard> shards;          // the shards this process scans
+  size_t rec_stride = 0;              // records of one shard's scan
+  size_t db_row_bytes = 0, tile_bytes = 0;  // one stored DB row (hi+lo f16 / fp32 per column) / tile
+  int qtmax = 0;                      // query tiles of one scan launch's block
+  int stride = 0;                     // option "time_dist": every stride-th step is sampled (0: none)
+};
+
+static int plan_shards(ia_ctx *c, const ia_level_args *args, int J, LevelPlan &P) {
   const ia_level_args *a = &args[0];
   int rc;
-  for (int j = 0; j < n_jobs; j++) {
-    const ia_level_args *x = &args[j];
-    if ((rc = check_level_args(x))) return rc;
-    if (x->ch != a->ch || x->n_ap != a->n_ap || x->a_h != a->a_h || x->a_w != a->a_w || x->b_h != a->b_h ||
-        x->b_w != a->b_w || x->mem != a->mem)
-      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch has the same shapes, channels and mem kind");
-    if (x->A != a->A || x->Ac != a->Ac || x->Ap != a->Ap || x->Apc != a->Apc)
-      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch shares the A side (same A / A' buffers)");
-  }
-  HIP_TRY(hipSetDevice(c->dev));
-  const int J = n_jobs;
-
-  LevelGeo g;
+  LevelGeo &g = P.g;
   g.pos2row = nullptr;
   g.ch = a->ch;
   g.D = 55 * a->ch;
   g.KH = kh_for(g.D + 1);
-  const int DP = 2 * g.KH;
+  P.J = J;
+  P.DP = 2 * g.KH;
   g.n_ap = a->n_ap;
   g.ah = a->a_h;
   g.aw = a->a_w;
@@ -840,54 +844,159 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
   // profiles/r03/shard); option "shard_unpruned" = 1 shards those too (tests, very large DBs).
   const bool shard_here = c->shard_unpruned ||
                           (c->prune && c->matcher == IA_MATCH_F16X3 && g.ch == 1 && g.NA >= c->prune_min_rows);
-  const bool sharded = shard_here && shard_level(g.n_tiles, c->world);
-  const bool emulated = shard_here && !sharded && c->world == 1 && c->shard_emulate > 1 &&
-                        shard_level(g.n_tiles, c->shard_emulate);
-  const int Wsh = sharded ? c->world : emulated ? c->shard_emulate : 1;  // shards of this level
-  const bool multi = Wsh > 1;
-  const bool xchg = multi && c->exchange == 1;  // peer-write winner exchange (k_merge_xchg)
-  // owner-computes sharded step (exchange = 2, ia_internal.h XOLayout): a rank brings its own
-  // job (emulated: one job per shard); checked against the pruned scan below
-  const bool xo = multi && c->exchange == 2;
-  if (xo) {
-    if (sharded && !c->xpeer[0]) return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2 needs ia_xchg_open");
-    if (Wsh > IA_XCHG_MAXW) return fail(IA_EINVAL, "ia_synthesize_level: the owner exchange takes <= 16 shards");
-    if (sharded && J != 1) return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2 takes the rank's own job (n_jobs = 1)");
-    if (emulated && J != Wsh)
+  P.sharded = shard_here && shard_level(g.n_tiles, c->world);
+  P.emulated = shard_here && !P.sharded && c->world == 1 && c->shard_emulate > 1 && shard_level(g.n_tiles, c->shard_emulate);
+  P.Wsh = P.sharded ? c->world : P.emulated ? c->shard_emulate : 1;
+  P.multi = P.Wsh > 1;
+  P.xchg = P.multi && c->exchange == 1;
+  // owner-computes: a rank brings its own job (emulated: one job per shard); checked against the
+  // pruned scan in plan_scan
+  P.xo = P.multi && c->exchange == 2;
+  if (P.xo) {
+    if (P.sharded && !c->xpeer[0]) return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2 needs ia_xchg_open");
+    if (P.Wsh > IA_XCHG_MAXW) return fail(IA_EINVAL, "ia_synthesize_level: the owner exchange takes <= 16 shards");
+    if (P.sharded && J != 1) return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2 takes the rank's own job (n_jobs = 1)");
+    if (P.emulated && J != P.Wsh)
       return fail(IA_EINVAL, "ia_synthesize_levels: emulated exchange = 2 takes one job per shard (n_jobs = shard_emulate)");
-    if (emulated && (rc = xchg_alloc(c, Wsh))) return rc;
+    if (P.emulated && (rc = xchg_alloc(c, P.Wsh))) return rc;
     if ((rc = c->xo_inv.ensure((size_t)IA_XO_MAXT * IA_TILE * 4))) return rc;
     HIP_TRY(hipMemsetAsync(c->xerr.p, 0, 4, c->st));
   }
-  if (xchg) {
-    if (sharded && !c->xpeer[0]) return fail(IA_EINVAL, "ia_synthesize_level: exchange = 1 needs ia_xchg_open");
-    if (Wsh > IA_XCHG_MAXW) return fail(IA_EINVAL, "ia_synthesize_level: the peer-write exchange takes <= 16 shards");
-    if (emulated && (rc = xchg_alloc(c, Wsh))) return rc;
+  if (P.xchg) {
+    if (P.sharded && !c->xpeer[0]) return fail(IA_EINVAL, "ia_synthesize_level: exchange = 1 needs ia_xchg_open");
+    if (P.Wsh > IA_XCHG_MAXW) return fail(IA_EINVAL, "ia_synthesize_level: the peer-write exchange takes <= 16 shards");
+    if (P.emulated && (rc = xchg_alloc(c, P.Wsh))) return rc;
     if ((int64_t)std::min(g.bh, (g.bw + 2) / 3) * J > IA_XCHG_MAXQ)
       return fail(IA_EINVAL, "ia_synthesize_level: wavefront steps (all jobs) wider than the exchange slots");
     HIP_TRY(hipMemsetAsync(c->xerr.p, 0, 4, c->st));
   }
   for (int j = 0; j < J; j++)
-    if (multi && args[j].dbg_src)
+    if (P.multi && args[j].dbg_src)
       return fail(IA_EINVAL, "ia_synthesize_level: debug outputs are produced by single-rank levels only");
-  {
-    int64_t t0 = 0, t1 = g.n_tiles;  // this rank's contiguous DB tiles (unpruned sharded levels hold only those)
-    if (sharded) ia_shard_tiles(g.NA, c->world, c->rank, &t0, &t1);
-    g.tile0 = (int)t0;
-    g.tile1 = (int)t1;
-  }
+  int64_t t0 = 0, t1 = g.n_tiles;  // this rank's contiguous DB tiles (unpruned sharded levels hold only those)
+  if (P.sharded) ia_shard_tiles(g.NA, c->world, c->rank, &t0, &t1);
+  g.tile0 = (int)t0;
+  g.tile1 = (int)t1;
+  P.nA = (size_t)g.ah * g.aw * g.ch;
+  P.nAc = (size_t)g.ahc * g.awc * g.ch;
+  P.nB = (size_t)g.bh * g.bw * g.ch;
+  P.nBc = (size_t)g.bhc * g.bwc * g.ch;
+  P.NB = (int64_t)g.bh * g.bw;
+  return IA_OK;
+}
 
-  const size_t nA = (size_t)g.ah * g.aw * g.ch, nAc = (size_t)g.ahc * g.awc * g.ch;
-  const size_t nB = (size_t)g.bh * g.bw * g.ch, nBc = (size_t)g.bhc * g.bwc * g.ch;
-  const int64_t NB = (int64_t)g.bh * g.bw;
+static int plan_scan(ia_ctx *c, bool use_h, LevelPlan &P) {
+  LevelGeo &g = P.g;
+  const int J = P.J;
+  P.use_h = use_h;
+  g.KS = use_h ? ia_ks_for(g.ch) : 0;
+  // certified pruned scan (1 channel, large DBs; every query of a step sorted in one
+  // workgroup's LDS)
+  ia_wavefront_shape(g.bh, g.bw, &P.T, &P.Mmax);
+  P.Mtmax = P.Mmax * J;
+  // (exchange = 2 emulated: each owner's queries at its own tile-aligned offset j Mpad_j)
+  P.Mpad_max = std::max(tile_pad(P.Mtmax), P.xo ? J * tile_pad(P.Mmax) : 0);
+  P.prune = c->prune && use_h && g.ch == 1 && g.NA >= c->prune_min_rows && P.Mpad_max <= 4096 &&
+            (g.n_tiles + c->scan_wgs - 1) / c->scan_wgs <= IA_K3P_MAXK_LDS;
+  const bool prune = P.prune;
+  if (P.xo && !prune)
+    return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2 shards pruned levels only (1 channel, split-f16, <= 4096 "
+                           "queries per step)");
+  // owner-computes geometry (pads past an owner's QTj query tiles are never contracted)
+  if (P.xo) {
+    const int QTj = (int)(tile_pad(P.Mmax) / IA_TILE);
+    P.xo_bpj = (QTj + ia_k3h_qtmax(g.KS) - 1) / ia_k3h_qtmax(g.KS);
+    P.xo_QTx = (QTj + P.xo_bpj - 1) / P.xo_bpj;
+    P.xo_QTs = P.xo_bpj * P.xo_QTx;
+    if (P.Wsh * P.xo_QTs > IA_XO_MAXT || P.Wsh * P.xo_bpj > IA_NWG_H)
+      return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2: wavefront steps too wide for the exchange area");
+  }
+  // Pruned levels: every rank holds the whole Morton-sorted DB, its tiles stored shard by shard
+  // (ia_internal.h ia_shard_morton_tile: shard r = Morton tiles r, r + W, ...), and scans its own
+  // contiguous storage range.  Unpruned levels: contiguous tile ranges (ia_shard_tiles).
+  if (prune) {
+    g.tile0 = 0;
+    g.tile1 = g.n_tiles;
+  }
+  P.ns = g.tile1 - g.tile0;
+  auto decomp = [&](int t0, int t1) {
+    Shard d{t0, t1, 0, 0};
+    const int n = t1 - t0;
+    if (prune) d.nwg = std::min(c->scan_wgs, n);  // round-robin chunks: WG w owns tiles w + nwg*k
+    else {
+      d.tpw = use_h ? std::max(IA_WGH / IA_WAVE, (n + c->scan_wgs - 1) / c->scan_wgs) : std::max(4, (n + IA_WG_TARGET - 1) / IA_WG_TARGET);
+      d.nwg = (n + d.tpw - 1) / d.tpw;
+    }
+    return d;
+  };
+  if (!P.multi) {
+    P.shards.push_back(decomp(g.tile0, g.tile1));
+  } else {
+    for (int r = P.sharded ? c->rank : 0; r < (P.sharded ? c->rank + 1 : P.Wsh); r++) {
+      int64_t t0 = ia_shard_off(g.n_tiles, P.Wsh, r), t1 = ia_shard_off(g.n_tiles, P.Wsh, r + 1);
+      if (!prune) ia_shard_tiles(g.NA, P.Wsh, r, &t0, &t1);
+      P.shards.push_back(decomp((int)t0, (int)t1));
+    }
+  }
+  int nwg_max = 1;
+  for (const Shard &x : P.shards) nwg_max = std::max(nwg_max, x.nwg);
+  g.nwg = P.shards[0].nwg;
+  g.tiles_per_wg = P.shards[0].tpw;
+  P.rec_stride = (size_t)P.Mtmax * nwg_max;
+  P.db_row_bytes = use_h ? (size_t)16 * g.KS * 4 : (size_t)P.DP * 4;
+  P.tile_bytes = use_h ? (size_t)ia_k3h_tile_bytes(g.KS) : (size_t)IA_TILE * P.DP * 4;
+  P.qtmax = use_h ? ia_k3h_qtmax(g.KS) : ia_k3_qtmax(g.KH);
+  P.stride = c->time_dist > 0 ? c->time_dist : 0;
+  return IA_OK;
+}
+
+// per-level scratch
+static int ensure_scratch(ia_ctx *c, const LevelPlan &P) {
+  const LevelGeo &g = P.g;
+  const size_t Mp = (size_t)P.Mpad_max, nsh = P.shards.size();
+  int rc;
+  if ((rc = c->db.ensure((size_t)std::max(P.ns, 1) * IA_TILE * P.db_row_bytes)) || (rc = c->mu.ensure((16 + 4 * 3 * 128) * 8)) ||
+      (rc = c->db64.ensure((size_t)g.NA * ia_db64_stride(g.ch) * 8)) ||
+      (rc = c->Rbits.ensure(4)) || (rc = c->q64.ensure(Mp * g.D * 8 * 2)) ||
+      (rc = c->qn2.ensure(Mp * 8 * 2)) || (rc = c->qf.ensure(Mp * P.db_row_bytes)) ||
+      (rc = c->rec.ensure(P.rec_stride * nsh * 16)) || (rc = c->recT.ensure(P.rec_stride * nsh * 4)) ||
+      (rc = c->win.ensure((size_t)P.Mtmax * 16)) || (rc = c->allwin.ensure((size_t)P.Mtmax * 16 * P.Wsh)) ||
+      (rc = c->counters.ensure(5 * 8)) || (rc = c->pairs.ensure(6 * IA_NWG_H * 8)) ||
+      (rc = c->qinfo.ensure(P.prune ? Mp * 3 * 16 * 2 : 16)))
+    return rc;
+  if (P.prune && ((rc = c->qs_order.ensure(Mp * 4)) || (rc = c->qs_info.ensure(Mp * 3 * 16)) ||
+                  (rc = c->qs_frag.ensure(Mp * P.db_row_bytes)) || (rc = c->qs_tbox.ensure(Mp / IA_TILE * 3 * 16))))
+    return rc;
+  return IA_OK;
+}
+
+// ---- phase 2: staging -----------------------------------------------------------------------
+struct LevelInputs {
+  std::vector<JobPtrs> jp;  // per job: its B side on the device
+  Imgs Aim, Bim;            // the A side; the B shape (images per job: JobPtrs)
+  JobSet jobs() const { return JobSet{jp[0], dev_jobs, (int)jp.size()}; }
+  JobSet job(int j) const { return JobSet{jp[j], dev_jobs + j, 1}; }
+  const JobPtrs *dev_jobs = nullptr;
+};
+
+// the A side and the B side of every job (host buffers: one staging set per job)
+static int stage_level(ia_ctx *c, const ia_level_args *args, const LevelPlan &P, LevelInputs &in) {
+  const ia_level_args *a = &args[0];
+  const LevelGeo &g = P.g;
+  const int J = P.J;
+  const size_t nA = P.nA, nAc = P.nAc, nB = P.nB, nBc = P.nBc;
+  const int64_t NB = P.NB;
+  int rc;
   const void *dA, *dAc, *dAp, *dApc;
   if ((rc = stage(c, c->A, a->A, nA * 8, a->mem, &dA)) || (rc = stage(c, c->Ac, a->Ac, nAc * 8, a->mem, &dAc)) ||
       (rc = stage(c, c->Ap, a->Ap, nA * g.n_ap * 8, a->mem, &dAp)) ||
       (rc = stage(c, c->Apc, a->Apc, nAc * g.n_ap * 8, a->mem, &dApc)))
     return rc;
-  // the B side of every job (host buffers: one staging set per job)
+  in.Aim = Imgs{(const double *)dAc, (const double *)dA, (const double *)dApc, (const double *)dAp,
+                g.ah, g.aw, g.ahc, g.awc, (int64_t)nA, (int64_t)nAc};
+  in.Bim = Imgs{nullptr, nullptr, nullptr, nullptr, g.bh, g.bw, g.bhc, g.bwc, 0, 0};
   if ((int)c->jb.size() < J) c->jb.resize(J);
-  std::vector<JobPtrs> jp(J);
+  in.jp.resize(J);
   for (int j = 0; j < J; j++) {
     const ia_level_args *x = &args[j];
     JobBufs &b = c->jb[j];
@@ -896,13 +1005,14 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
         (rc = stage(c, b.Bpc, x->Bpc, nBc * 8, x->mem, &dBpc)) || (rc = stage(c, b.W, x->weights, (size_t)g.D * 8, x->mem, &dW)) ||
         (rc = b.pstat.ensure((size_t)NB * 4)))
       return rc;
-    JobPtrs &p = jp[j];
+    JobPtrs &p = in.jp[j];
     p.Bc = (const double *)dBc;
     p.B = (const double *)dB;
     p.Bpc = (const double *)dBpc;
     p.weights = (const double *)dW;
     p.kf = x->kappa_factor;
     p.pstat = b.pstat.as<unsigned>();
+    p.nn = nullptr;
     if (x->mem == IA_MEM_DEVICE) {
       p.Bp = x->Bp;
       p.s = x->s_out;
@@ -925,134 +1035,93 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
     }
     HIP_TRY(hipMemsetAsync(p.pstat, 0, (size_t)NB * 4, c->st));
   }
+  return IA_OK;
+}
 
-  // matcher: split-f16 when the channel count has a K3h instance and every image value fits
-  // (IA_F16_MAXABS, one 4-byte read-back per level); otherwise the fp32 MFMA scan
-  bool use_h = false;
-  if (c->matcher == IA_MATCH_F16X3 && ia_ks_for(g.ch) > 0) {
-    if ((rc = c->absmax.ensure(4))) return rc;
-    HIP_TRY(hipMemsetAsync(c->absmax.p, 0, 4, c->st));
-    for (int j = 0; j < J; j++) {
-      const double *arrs[8] = {j ? nullptr : (const double *)dA, j ? nullptr : (const double *)dAc,
-                               j ? nullptr : (const double *)dAp, j ? nullptr : (const double *)dApc,
-                               jp[j].B, jp[j].Bc, jp[j].Bpc, jp[j].Bp};
-      const int64_t ns8[8] = {(int64_t)nA, (int64_t)nAc, (int64_t)(nA * g.n_ap), (int64_t)(nAc * g.n_ap),
-                              (int64_t)nB, (int64_t)nBc, (int64_t)nBc, (int64_t)nB};
-      ia_launch_absmax(arrs, ns8, c->absmax.as<unsigned>(), c->st);
-    }
-    unsigned mbits = 0;
-    HIP_TRY(hipMemcpyAsync(&mbits, c->absmax.p, 4, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    float mx;
-    std::memcpy(&mx, &mbits, 4);
-    use_h = mx <= IA_F16_MAXABS;
+// matcher: split-f16 when the channel count has a K3h instance and every image value fits
+// (IA_F16_MAXABS, one 4-byte read-back per level); otherwise the fp32 MFMA scan
+static int probe_matcher(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, bool *use_h) {
+  const LevelGeo &g = P.g;
+  *use_h = false;
+  if (c->matcher != IA_MATCH_F16X3 || ia_ks_for(g.ch) <= 0) return IA_OK;
+  int rc;
+  if ((rc = c->absmax.ensure(4))) return rc;
+  HIP_TRY(hipMemsetAsync(c->absmax.p, 0, 4, c->st));
+  const Imgs &A = in.Aim;
+  for (int j = 0; j < P.J; j++) {
+    const JobPtrs &p = in.jp[j];
+    const double *arrs[8] = {j ? nullptr : A.p1, j ? nullptr : A.p0, j ? nullptr : A.p3, j ? nullptr : A.p2, p.B, p.Bc, p.Bpc, p.Bp};
+    const int64_t ns8[8] = {(int64_t)P.nA, (int64_t)P.nAc, (int64_t)(P.nA * g.n_ap), (int64_t)(P.nAc * g.n_ap),
+                            (int64_t)P.nB, (int64_t)P.nBc, (int64_t)P.nBc, (int64_t)P.nB};
+    ia_launch_absmax(arrs, ns8, c->absmax.as<unsigned>(), c->st);
   }
-  g.KS = use_h ? ia_ks_for(g.ch) : 0;
-  // certified pruned scan (1 channel, large DBs; every query of a step sorted in one
-  // workgroup's LDS)
-  int64_t T, Mmax;
-  ia_wavefront_shape(g.bh, g.bw, &T, &Mmax);
-  const int64_t Mtmax = Mmax * J;  // queries of the widest step over all jobs
-  // (exchange = 2 emulated: each owner's queries at its own tile-aligned offset j Mpad_j)
-  const int64_t Mpad_max = std::max((Mtmax + IA_TILE - 1) / IA_TILE * IA_TILE,
-                                    xo ? J * ((Mmax + IA_TILE - 1) / IA_TILE * IA_TILE) : 0);
-  const bool prune = c->prune && use_h && g.ch == 1 && g.NA >= c->prune_min_rows && Mpad_max <= 4096 &&
-                     (g.n_tiles + c->scan_wgs - 1) / c->scan_wgs <= IA_K3P_MAXK_LDS;
-  // option "nn_bound": per-pixel exact NN rows of a pruned one-rank level (-1 until merged)
-  for (int j = 0; j < J; j++) {
-    jp[j].nn = nullptr;
-    if (prune && c->nn_bound) {  // (every merge form writes it: fused, owner-computes, exchange finishes)
-      JobBufs &b = c->jb[j];
-      if ((rc = b.NN.ensure((size_t)NB * 4))) return rc;
-      jp[j].nn = b.NN.as<int32_t>();
-      HIP_TRY(hipMemsetAsync(jp[j].nn, 0xFF, (size_t)NB * 4, c->st));
-    }
-  }
-  if ((rc = c->jobs.ensure(sizeof(JobPtrs) * J))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->jobs.p, jp.data(), sizeof(JobPtrs) * J, hipMemcpyHostToDevice, c->st));
-  const JobSet djobs{jp[0], c->jobs.as<JobPtrs>(), J};
-  if (xo && !prune)
-    return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2 shards pruned levels only (1 channel, split-f16, <= 4096 "
-                           "queries per step)");
-  // owner-computes geometry: per owner QTj query tiles in bpj blocks of QTx tiles, QTs = bpj QTx
-  // tiles per owner in the step layout (pads past QTj never contracted)
-  int xo_bpj = 1, xo_QTx = 1, xo_QTs = 1;
-  if (xo) {
-    const int QTj = (int)((Mmax + IA_TILE - 1) / IA_TILE);
-    xo_bpj = (QTj + ia_k3h_qtmax(g.KS) - 1) / ia_k3h_qtmax(g.KS);
-    xo_QTx = (QTj + xo_bpj - 1) / xo_bpj;
-    xo_QTs = xo_bpj * xo_QTx;
-    if (Wsh * xo_QTs > IA_XO_MAXT || Wsh * xo_bpj > IA_NWG_H)
-      return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2: wavefront steps too wide for the exchange area");
-  }
-  // Pruned levels: every rank holds the whole Morton-sorted DB, its tiles stored shard by shard
-  // (ia_internal.h ia_shard_morton_tile: shard r = Morton tiles r, r + W, ...), and scans its own
-  // contiguous storage range.  Unpruned levels: contiguous tile ranges (ia_shard_tiles).
-  if (prune) {
-    g.tile0 = 0;
-    g.tile1 = g.n_tiles;
-  }
-  const int ns = g.tile1 - g.tile0;  // DB tiles this process holds
-  struct Shard {
-    int t0, t1, nwg, tpw;  // storage tiles [t0, t1) of the level's DB, scan decomposition
-  };
-  auto decomp = [&](int t0, int t1) {
-    Shard d{t0, t1, 0, 0};
-    const int n = t1 - t0;
-    if (prune) d.nwg = std::min(c->scan_wgs, n);  // round-robin chunks: WG w owns tiles w + nwg*k
-    else {
-      d.tpw = use_h ? std::max(IA_WGH / IA_WAVE, (n + c->scan_wgs - 1) / c->scan_wgs) : std::max(4, (n + IA_WG_TARGET - 1) / IA_WG_TARGET);
-      d.nwg = (n + d.tpw - 1) / d.tpw;
-    }
-    return d;
-  };
-  std::vector<Shard> shards;  // the shards this process scans
-  if (!multi) {
-    shards.push_back(decomp(g.tile0, g.tile1));
-  } else {
-    for (int r = sharded ? c->rank : 0; r < (sharded ? c->rank + 1 : Wsh); r++) {
-      if (prune) {
-        const int t0 = (int)ia_shard_off(g.n_tiles, Wsh, r), t1 = (int)ia_shard_off(g.n_tiles, Wsh, r + 1);
-        shards.push_back(decomp(t0, t1));
-      } else {
-        int64_t t0, t1;
-        ia_shard_tiles(g.NA, Wsh, r, &t0, &t1);
-        shards.push_back(decomp((int)t0, (int)t1));
-      }
-    }
-  }
-  int nwg_max = 1;
-  for (const Shard &x : shards) nwg_max = std::max(nwg_max, x.nwg);
-  g.nwg = shards[0].nwg;
-  g.tiles_per_wg = shards[0].tpw;
-  const size_t rec_stride = (size_t)Mtmax * nwg_max;  // records of one shard's scan
-  const size_t db_row_bytes = use_h ? (size_t)16 * g.KS * 4 : (size_t)DP * 4;  // hi+lo f16 / fp32 per column
-  const size_t tile_bytes = use_h ? (size_t)ia_k3h_tile_bytes(g.KS) : (size_t)IA_TILE * DP * 4;  // one stored DB tile
+  unsigned mbits = 0;
+  HIP_TRY(hipMemcpyAsync(&mbits, c->absmax.p, 4, hipMemcpyDeviceToHost, c->st));
+  HIP_TRY(hipStreamSynchronize(c->st));
+  float mx;
+  std::memcpy(&mx, &mbits, 4);
+  *use_h = mx <= IA_F16_MAXABS;
+  return IA_OK;
+}
 
-  // per-level scratch
-  if ((rc = c->db.ensure((size_t)std::max(ns, 1) * IA_TILE * db_row_bytes)) || (rc = c->mu.ensure((16 + 4 * 3 * 128) * 8)) ||
-      (rc = c->db64.ensure((size_t)g.NA * ia_db64_stride(g.ch) * 8)) ||
-      (rc = c->Rbits.ensure(4)) || (rc = c->q64.ensure((size_t)Mpad_max * g.D * 8 * 2)) ||
-      (rc = c->qn2.ensure((size_t)Mpad_max * 8 * 2)) || (rc = c->qf.ensure((size_t)Mpad_max * db_row_bytes)) ||
-      (rc = c->rec.ensure(rec_stride * shards.size() * 16)) || (rc = c->recT.ensure(rec_stride * shards.size() * 4)) ||
-      (rc = c->win.ensure((size_t)Mtmax * 16)) || (rc = c->allwin.ensure((size_t)Mtmax * 16 * Wsh)) ||
-      (rc = c->counters.ensure(5 * 8)) ||
-      (rc = c->pairs.ensure(6 * IA_NWG_H * 8)) || (rc = c->ord.ensure(2 * 4096 * 4)) ||
-      (rc = c->qinfo.ensure(prune ? (size_t)Mpad_max * 3 * 16 * 2 : 16)))
-    return rc;
-  if (prune && ((rc = c->qs_order.ensure((size_t)Mpad_max * 4)) || (rc = c->qs_info.ensure((size_t)Mpad_max * 3 * 16)) ||
-                (rc = c->qs_frag.ensure((size_t)Mpad_max * db_row_bytes)) ||
-                (rc = c->qs_tbox.ensure((size_t)Mpad_max / IA_TILE * 3 * 16))))
-    return rc;
-  // option "stamps" (pruned levels): per-launch workgroup stamps of every K3p launch (<= IA_NWG_H
-  // workgroups each) and every fused merge launch (<= Mpad_max + J + 1 workgroups)
-  const bool stamped = c->stamps && prune;
-  const int64_t k3_cap = T * (int64_t)shards.size() * (c->k3p_blocks ? 1 : 8);
-  const int mg_stride = (int)Mpad_max + J + 64;
-  const int64_t mg_cap = T * (xo ? J : 1);  // merge launches per step: one, or one per owned job (exchange 2)
-  int64_t k3_n = 0, mg_n = 0;
-  if (stamped) {
-    // the slots start zeroed (fresh buffers here; the slots a level used are cleared after it)
+// option "nn_bound": per-pixel exact NN rows of a pruned one-rank level (-1 until merged; every
+// merge form writes it: fused, owner-computes, exchange finishes); then the device JobPtrs table
+static int stage_jobs(ia_ctx *c, const LevelPlan &P, LevelInputs &in) {
+  int rc;
+  for (int j = 0; j < P.J && P.prune && c->nn_bound; j++) {
+    JobBufs &b = c->jb[j];
+    if ((rc = b.NN.ensure((size_t)P.NB * 4))) return rc;
+    in.jp[j].nn = b.NN.as<int32_t>();
+    HIP_TRY(hipMemsetAsync(in.jp[j].nn, 0xFF, (size_t)P.NB * 4, c->st));
+  }
+  if ((rc = c->jobs.ensure(sizeof(JobPtrs) * P.J))) return rc;
+  HIP_TRY(hipMemcpyAsync(c->jobs.p, in.jp.data(), sizeof(JobPtrs) * P.J, hipMemcpyHostToDevice, c->st));
+  in.dev_jobs = c->jobs.as<JobPtrs>();
+  return IA_OK;
+}
+
+// ---- phase 3: the DB ------------------------------------------------------------------------
+// means, the fp64 row DB (K1b: every row, coherence reads any row), the pruned scan's table
+// (sets g.pos2row, *ufac) and this process's tiles (K1), bracketed by lv0 / kb[0..3] / lv1
+static int build_level_db(ia_ctx *c, LevelPlan &P, const LevelInputs &in, double *ufac) {
+  LevelGeo &g = P.g;
+  int rc;
+  HIP_TRY(hipEventRecord(c->lv0, c->st));
+  ia_launch_means(g.ch, in.Aim, g.n_ap, c->mu.as<double>(), c->st);
+  HIP_TRY(hipEventRecord(c->kb[0], c->st));
+  ia_launch_db64_build(g, in.Aim, c->db64.as<double>(), c->st);
+  HIP_TRY(hipEventRecord(c->kb[1], c->st));
+  *ufac = 0.;
+  if (P.prune && (rc = prepare_prune(c, g, c->mu.as<double>(), P.Wsh, ufac))) return rc;
+  HIP_TRY(hipEventRecord(c->kb[2], c->st));
+  if (P.ns > 0) {
+    if (P.use_h) ia_launch_db_build_h(g, in.Aim, c->db64.as<double>(), c->mu.as<double>(), c->db.p, c->Rbits.as<unsigned>(), c->st);
+    else ia_launch_db_build(g, in.Aim, c->mu.as<double>(), c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
+  }
+  HIP_TRY(hipEventRecord(c->kb[3], c->st));
+  HIP_TRY(hipEventRecord(c->lv1, c->st));
+  return IA_OK;
+}
+
+// ---- what the steps share -------------------------------------------------------------------
+// Option "stamps" (pruned levels): per-launch workgroup stamps of every K3p launch (<= IA_NWG_H
+// workgroups each) and every fused merge launch (<= Mpad_max + J + 1 workgroups).  The slots
+// start zeroed (fresh buffers here), and the slots a level wrote are cleared on EVERY exit
+// (an early error return after some stamped launches left non-zero slots that a
+// later, smaller launch would have read).
+struct StampSlots {
+  ia_ctx *c = nullptr;
+  bool on = false;
+  int64_t k3_cap = 0, mg_cap = 0, k3_n = 0, mg_n = 0;
+  int mg_stride = 0;
+  int open(ia_ctx *ctx, const LevelPlan &P) {
+    c = ctx;
+    on = c->stamps && P.prune;
+    k3_cap = P.T * (int64_t)P.shards.size() * (c->k3p_blocks ? 1 : 8);
+    mg_stride = (int)P.Mpad_max + P.J + 64;
+    mg_cap = P.T * (P.xo ? P.J : 1);  // merge launches per step: one, or one per owned job (exchange 2)
+    if (!on) return IA_OK;
+    int rc;
     const size_t k3b = (size_t)k3_cap * IA_NWG_H * 16, mgb = (size_t)mg_cap * mg_stride * 16;
     const bool fresh_k3 = c->stamp_k3.cap < k3b, fresh_mg = c->stamp_mg.cap < mgb;
     if ((rc = c->stamp_k3.ensure(k3b)) || (rc = c->stamp_mg.ensure(mgb)) ||
@@ -1060,203 +1129,71 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
       return rc;
     if (fresh_k3) HIP_TRY(hipMemsetAsync(c->stamp_k3.p, 0, c->stamp_k3.cap, c->st));
     if (fresh_mg) HIP_TRY(hipMemsetAsync(c->stamp_mg.p, 0, c->stamp_mg.cap, c->st));
+    return IA_OK;
   }
-  auto k3_stamp = [&]() -> unsigned long long * {
-    return stamped && k3_n < k3_cap ? c->stamp_k3.as<unsigned long long>() + (size_t)2 * IA_NWG_H * k3_n++ : nullptr;
-  };
-  auto mg_stamp = [&]() -> unsigned long long * {
-    return stamped && mg_n < mg_cap ? c->stamp_mg.as<unsigned long long>() + (size_t)2 * mg_stride * mg_n++ : nullptr;
-  };
-  // the slots this level wrote are cleared on EVERY exit (an early error return after
-  // some stamped launches left non-zero slots that a later, smaller launch would have read)
-  struct StampClear {
-    ia_ctx *c;
-    const int64_t &k3_n, &mg_n;
-    int mg_stride;
-    ~StampClear() {
-      if (k3_n) (void)hipMemsetAsync(c->stamp_k3.p, 0, (size_t)k3_n * IA_NWG_H * 16, c->st);
-      if (mg_n) (void)hipMemsetAsync(c->stamp_mg.p, 0, (size_t)mg_n * mg_stride * 16, c->st);
-    }
-  } stamp_clear{c, k3_n, mg_n, mg_stride};
-  double bytes_all_fixed = 0.;  // algorithmic bytes of every pruned launch besides its DB tiles
-  double db_cap_all = 0.;       // the whole tiles of every pruned launch's DB range, each counted once
-                                // (a launch of nqb query blocks streams a tile once per block)
-  // per-workgroup counters of the pruned scan: [pairs | pairs (timed steps) | tiles | tiles (timed) |
-  // extra half-tiles | extra half-tiles (timed)][wg]
-  HIP_TRY(hipMemsetAsync(c->pairs.p, 0, 6 * IA_NWG_H * 8, c->st));
-  HIP_TRY(hipMemsetAsync(c->Rbits.p, 0, 4, c->st));
-  HIP_TRY(hipMemsetAsync(c->counters.p, 0, 5 * 8, c->st));
-
-  Imgs Aim{(const double *)dAc, (const double *)dA, (const double *)dApc, (const double *)dAp,
-           g.ah, g.aw, g.ahc, g.awc, (int64_t)nA, (int64_t)nAc};
-  Imgs Bim{nullptr, nullptr, nullptr, nullptr, g.bh, g.bw, g.bhc, g.bwc, 0, 0};  // images per job (JobPtrs)
-
-  HIP_TRY(hipEventRecord(c->lv0, c->st));
-  ia_launch_means(g.ch, Aim, g.n_ap, c->mu.as<double>(), c->st);
-  HIP_TRY(hipEventRecord(c->kb[0], c->st));
-  ia_launch_db64_build(g, Aim, c->db64.as<double>(), c->st);  // every row: coherence reads any row
-  HIP_TRY(hipEventRecord(c->kb[1], c->st));
-  double ufac = 0.;
-  if (prune && (rc = prepare_prune(c, g, c->mu.as<double>(), Wsh, &ufac)))
-    return rc;  // sets g.pos2row
-  HIP_TRY(hipEventRecord(c->kb[2], c->st));
-  if (ns > 0) {
-    if (use_h) ia_launch_db_build_h(g, Aim, c->db64.as<double>(), c->mu.as<double>(), c->db.p, c->Rbits.as<unsigned>(), c->st);
-    else ia_launch_db_build(g, Aim, c->mu.as<double>(), c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
+  unsigned long long *k3() {  // the next scan launch's slots (nullptr: not stamped)
+    return on && k3_n < k3_cap ? c->stamp_k3.as<unsigned long long>() + (size_t)2 * IA_NWG_H * k3_n++ : nullptr;
   }
-  HIP_TRY(hipEventRecord(c->kb[3], c->st));
-  HIP_TRY(hipEventRecord(c->lv1, c->st));
-
-  MergeArgs ma;
-  ma.db64 = c->db64.as<double>();
-  ma.rec = c->rec.as<float4>();
-  ma.recT = c->recT.as<float>();
-  ma.q64 = c->q64.as<double>();
-  ma.qn2 = c->qn2.as<double>();
-  ma.Rbits = c->Rbits.as<unsigned>();
-  ma.nwg = g.nwg;
-  ma.tpw = g.tiles_per_wg;
-  ma.pos0 = g.tile0 * IA_TILE;
-  ma.pos_end = g.tile1 * IA_TILE;
-  ma.NT = g.n_tiles;
-  ma.NA = (int)g.NA;
-  ma.pos2row = g.pos2row;
-  ma.rr = prune ? 1 : 0;
-  ma.qinfo = prune ? c->qinfo.as<float4>() : nullptr;
-  ma.boxes = prune ? c->boxes.as<float4>() : nullptr;
-  ma.ufac = ufac;
-  ma.img_rows = (c->row_source == 1 && g.ch == 1) ? 1 : 0;
-  ma.eps_c = use_h ? ia_eps_c_h(g.KS, prune || c->k3_variant == 1) : ia_eps_c(DP);
-  ma.eps_a = use_h ? ia_eps_a_h() : 0.;
-  // per shard: its records, decomposition, DB positions (and table / boxes of a pruned level)
-  std::vector<MergeArgs> mas(shards.size(), ma);
-  std::vector<int64_t> shard_rows(shards.size(), 0);  // real DB rows in each shard (unpruned flops)
-  for (size_t i = 0; i < shards.size(); i++) {
-    const Shard &x = shards[i];
-    MergeArgs &m = mas[i];
-    m.rec = c->rec.as<float4>() + i * rec_stride;
-    m.recT = c->recT.as<float>() + i * rec_stride;
-    m.nwg = x.nwg;
-    m.tpw = x.tpw;
-    m.pos0 = x.t0 * IA_TILE;
-    m.pos_end = x.t1 * IA_TILE;
-    if (prune) {
-      m.pos2row = g.pos2row + (size_t)x.t0 * IA_TILE;
-      m.boxes = c->boxes.as<float4>() + 2 * (size_t)x.t0;
-      m.NT = x.t1 - x.t0;
-    }
-    for (int t = x.t0; t < x.t1 && !prune; t++) {
-      const int64_t tr = ia_tile_perm(t, g.n_tiles);
-      shard_rows[i] += std::min<int64_t>(IA_TILE, (g.NA - tr + g.n_tiles - 1) / g.n_tiles);
-    }
+  unsigned long long *mg() {  // the next merge launch's
+    return on && mg_n < mg_cap ? c->stamp_mg.as<unsigned long long>() + (size_t)2 * mg_stride * mg_n++ : nullptr;
   }
-
-  const int qtmax = use_h ? ia_k3h_qtmax(g.KS) : ia_k3_qtmax(g.KH);
-  const int stride = c->time_dist > 0 ? c->time_dist : 0;
-  // fused K4(t) + K2p(t + 1) (option "fuse_gather", ia_kernels.hip k_merge_gather): one-job
-  // unsharded pruned levels (<= 256 records per query: one launch's chunks, or nch <= 256 of a
-  // wide step's 2-D launch); the query buffers alternate by step parity
-  static_assert(IA_NWG_H <= 4 * IA_WAVE, "k_merge_gather reads 4 records per lane");
-  // (owner-computes steps too: each local owner's merge + its next gather, which publishes)
-  // (batched jobs: one handoff row set per job.  Unpruned levels - K2h fused, option
-  // "fuse_unpruned" - measured slower: their longer fused launches delay the pipelined finest
-  // level's scans, and cfg5's batched 512^2 steps lose 1-2 %)
-  bool chain = c->fuse_gather && use_h && g.ch == 1 && ma.img_rows == 0 && g.bw >= 3 &&
-               (prune || c->fuse_unpruned) && ((!multi && !xo && mas[0].nwg <= 4 * IA_WAVE) || (xo && prune));
-  // (one-rank levels: the process-wide chained-wave budget, g_chain_waves; a launch holds at most
-  // Mpad + J waves: merges, entering rows, pads)
-  // Owner-computes levels (exchange 2) take the same reservation: their fused launches chain
-  // rows like any other (and wait for peers' records besides, which never depend on a chained
-  // wave of this process), so the same budget keeps them deadlock-free
-  ChainReservation chain_res;
-  if (chain && !chain_res.take((int)(Mpad_max + J) + (xo ? 1 : 0), c->chain_budget)) chain = false;
-  if (chain) {
-    const int hrows = g.bh * J;  // per job (local owner)
-    if (c->hand_rows < hrows) {
-      HIP_TRY(hipStreamSynchronize(c->st));
-      if (c->hand) hipFree(c->hand);
-      c->hand = nullptr;
-      c->hand_rows = 0;
-      HIP_TRY(hipExtMallocWithFlags((void **)&c->hand, (size_t)hrows * sizeof(HandSlot), hipDeviceMallocUncached));
-      HIP_TRY(hipMemset(c->hand, 0, (size_t)hrows * sizeof(HandSlot)));
-      HIP_TRY(hipDeviceSynchronize());
-      c->hand_rows = hrows;
-    }
-    if (c->kslot_n < Mpad_max) {  // key slots of the gathers' sort (option "fuse_sort")
-      HIP_TRY(hipStreamSynchronize(c->st));
-      if (c->kslot) hipFree(c->kslot);
-      c->kslot = nullptr;
-      c->kslot_n = 0;
-      HIP_TRY(hipExtMallocWithFlags((void **)&c->kslot, (size_t)Mpad_max * 8, hipDeviceMallocUncached));
-      HIP_TRY(hipMemset(c->kslot, 0, (size_t)Mpad_max * 8));
-      HIP_TRY(hipDeviceSynchronize());
-      c->kslot_n = (int)Mpad_max;
-    }
-    if ((rc = c->xerr.ensure(4))) return rc;
-    HIP_TRY(hipMemsetAsync(c->xerr.p, 0, 4, c->st));
+  void durations() {  // per-launch device ticks: K3p launches first, then the merges
+    if (!on) return;
+    unsigned long long *dur = c->stamp_dur.as<unsigned long long>();
+    ia_launch_stamp_durations(c->stamp_k3.as<unsigned long long>(), (int)k3_n, IA_NWG_H, dur, c->st, dur + 2 * (k3_n + mg_n));
+    ia_launch_stamp_durations(c->stamp_mg.as<unsigned long long>(), (int)mg_n, mg_stride, dur + 2 * k3_n, c->st);
   }
-  // query buffers of step t (chain: parity half t & 1)
-  auto qhalf = [&](int64_t t, double *&q64, double *&qn2, float4 *&qinfo) {
-    const size_t h = chain && (t & 1) ? 1 : 0;
-    q64 = c->q64.as<double>() + h * Mpad_max * g.D;
-    qn2 = c->qn2.as<double>() + h * Mpad_max;
-    qinfo = prune ? c->qinfo.as<float4>() + h * 3 * Mpad_max : nullptr;
-  };
-  int64_t gathered = -1;  // the step whose gather the previous fused launch ran
-  bool gsort = false;     // ... and that launch also sorted it (option "fuse_sort": no K2s, no in-scan sort)
-  // (the gathers' sort waits for every wave of its launch: only while all chained waves in flight
-  // fit the resident slots, half the budget)
-  const bool fsort = chain && prune && !xo && (c->fuse_sort == 1 || (c->fuse_sort == 2 && Mtmax >= IA_FUSE_SORT_MINQ)) &&
-                     g_chain_waves.load() <= c->chain_budget / 2;
-  const int64_t n_timed = stride ? (T + stride - 1) / stride : 0;
-  for (auto *v : {&c->evs, &c->evg, &c->evm})
-    if ((int64_t)v->size() < 2 * n_timed) {
-      size_t old = v->size();
-      v->resize(2 * n_timed);
-      for (size_t i = old; i < v->size(); i++) hipEventCreate(&(*v)[i]);
-    }
-  // algorithmic bytes of one query's gather (K2h / K2p): its 55*ch features read, (K2p) the 12
-  // causal coherence candidates' fp64 rows for U, the fp64 row + MFMA fragments + |q'|^2 (+ K2p's
-  // pruning record) written
-  const double gq_bytes = 55.0 * g.ch * 8 + (prune ? 12.0 * ia_db64_stride(g.ch) * 8 : 0.) + g.D * 8.0 +
-                          (use_h ? 16.0 * g.KS * 4 : DP * 4.0) + 8.0 + (prune ? 48.0 : 0.);
-  int64_t n_gm = 0;                        // sampled steps (gather / merge brackets)
-  double gather_bytes_timed = 0.;
-  int64_t dist_launches = 0, launches_timed = 0, n_rec = 0;
-  double dist_flops = 0., flops_timed = 0., pairs_full = 0., tiles_full = 0., bytes_timed_fixed = 0.;
-  int ord_n = 0;  // pruned scan (k3p_variant 8): queries in the previous step's key order
-  // level pipelining: this level's per-step events (recording) / waits on the previous level
-  const int gen = c->p_record ? c->p_gen.load() + 1 : 0;
+  ~StampSlots() {
+    if (k3_n) (void)hipMemsetAsync(c->stamp_k3.p, 0, (size_t)k3_n * IA_NWG_H * 16, c->st);
+    if (mg_n) (void)hipMemsetAsync(c->stamp_mg.p, 0, (size_t)mg_n * mg_stride * 16, c->st);
+  }
+};
+
+// Level pipelining: this level's per-step events (a recording context) and its
+// waits on the level before it (ia_pipeline_depend).  Every return after open() - errors too -
+// releases the dependents' waits (p_done).
+struct PipelineLink {
+  ia_ctx *c = nullptr;
+  int gen = 0;                      // this call's generation (0: not recording)
   std::vector<hipEvent_t> *pev = nullptr;
-  if (gen) {
-    pev = &c->p_ev[gen % 3];
-    while ((int64_t)pev->size() < T) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      pev->push_back(e);
-    }
-    c->p_enq.store(-1);
-    c->p_T.store(T);
-    c->p_gen.store(gen);  // published last: a dependent reads p_T / p_enq of this generation after it
-  }
-  struct PDone {  // every return from here on (errors too) releases the dependents' waits
-    ia_ctx *c;
-    int g;
-    ~PDone() {
-      if (g) c->p_done.store(g);
-    }
-  } pdone{c, gen};
-  ia_ctx *dp = c->dep;
-  const int dgen = c->dep_gen;
-  c->dep = nullptr;  // one level call per ia_pipeline_depend
-  c->dep_gen = 0;
+  bool no_events = false;           // option "pipeline_last": nothing waits on this call's steps
+  ia_ctx *dp = nullptr;             // the context of the level before, its generation
+  int dgen = 0;
   int64_t waited = -1;
   // the previous level's host thread stopped enqueueing (it failed): 120 s without progress of
   // its generation or its enqueued steps (a long but healthy predecessor keeps resetting this)
-  auto t_prog = std::chrono::steady_clock::now();
+  std::chrono::steady_clock::time_point t_prog;
   long long seen_enq = -2;
   int seen_gen = -1;
-  auto stalled = [&]() {
+
+  int open(ia_ctx *ctx, int64_t T) {
+    c = ctx;
+    const int g = c->p_record ? c->p_gen.load() + 1 : 0;
+    if (g) {
+      pev = &c->p_ev[g % 3];
+      while ((int64_t)pev->size() < T) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        pev->push_back(e);
+      }
+      c->p_enq.store(-1);
+      c->p_T.store(T);
+      c->p_gen.store(g);  // published last: a dependent reads p_T / p_enq of this generation after it
+    }
+    gen = g;
+    dp = c->dep;
+    dgen = c->dep_gen;
+    c->dep = nullptr;  // one level call per ia_pipeline_depend
+    c->dep_gen = 0;
+    t_prog = std::chrono::steady_clock::now();
+    no_events = c->p_last != 0;
+    c->p_last = 0;
+    return IA_OK;
+  }
+  ~PipelineLink() {
+    if (gen) c->p_done.store(gen);
+  }
+  bool stalled() {
     const auto now = std::chrono::steady_clock::now();
     const long long e = dp->p_enq.load();
     const int gn = dp->p_gen.load();
@@ -1267,8 +1204,9 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
       return false;
     }
     return now - t_prog > std::chrono::seconds(120);
-  };
-  auto wait_dep = [&](int64_t t) -> int {
+  }
+  // step t reads B' of the previous level's steps <= t / 2 + 4
+  int wait_dep(int64_t t) {
     if (!dp) return IA_OK;
     while (dp->p_gen.load() < dgen && dp->p_done.load() < dgen)  // it has started that level
       if (stalled()) return fail(IA_ECOMM, "pipeline: the previous level did not start");
@@ -1286,356 +1224,398 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
     }
     waited = need;
     return IA_OK;
-  };
-  const bool no_events = c->p_last != 0;  // nothing waits on this call's steps
-  c->p_last = 0;
-  auto mark_step = [&](int64_t t) {
+  }
+  void mark_step(int64_t t) {
     if (!gen) return;
     if (!no_events) hipEventRecord((*pev)[t], c->st);
     c->p_enq.store(t);
-  };
-  for (int64_t t = 0; t < T; mark_step(t), t++) {
-    if ((rc = wait_dep(t))) return rc;
+  }
+};
+
+// What the scan launches of a level add up to (ia_stats), and the event bracket of a sampled
+// step's scans.  Each launch states its own quantities: the (DB tile, query tile) pairs and tile
+// visits an unpruned scan would make, its MFMA flops (unpruned; the pruned kernels count their
+// pairs), and for a pruned launch the algorithmic bytes besides its DB stream - tile boxes, query
+// fragments and pruning records, K3 records written - and the whole tiles of its DB range.
+struct ScanTally {
+  ia_ctx *c;
+  int stride;
+  bool timed = false;           // the current step is sampled
+  int64_t n_rec = 0;            // sampled steps
+  int64_t dist_launches = 0, launches_timed = 0;
+  double dist_flops = 0., flops_timed = 0., pairs_full = 0., tiles_full = 0.;
+  double bytes_all_fixed = 0., bytes_timed_fixed = 0.;
+  double db_cap_all = 0.;       // each launch's tiles counted once (a launch of nqb query blocks streams a tile once per block)
+  void begin_step(int64_t t) {
+    timed = stride && t % stride == 0;
+    if (timed) hipEventRecord(c->evs[2 * n_rec], c->st);
+  }
+  void end_step() {
+    if (timed) hipEventRecord(c->evs[2 * n_rec++ + 1], c->st);
+  }
+  // per-workgroup counter slots of the pruned scan: [pairs | pairs (timed steps) | tiles | tiles
+  // (timed) | extra half-tiles | extra half-tiles (timed)][wg]
+  unsigned long long *pairs() const { return c->pairs.as<unsigned long long>() + (timed ? IA_NWG_H : 0); }
+  unsigned long long *tiles() const { return c->pairs.as<unsigned long long>() + (timed ? 3 : 2) * IA_NWG_H; }
+  void add(double pairs, double tile_visits, double flops, bool pruned, double fixed_bytes, double db_bytes) {
+    dist_flops += flops;
+    pairs_full += pairs;
+    tiles_full += tile_visits;
+    dist_launches++;
+    if (pruned) {
+      bytes_all_fixed += fixed_bytes;
+      db_cap_all += db_bytes;
+    }
+    if (timed) {
+      flops_timed += flops;
+      launches_timed++;
+      bytes_timed_fixed += fixed_bytes;
+    }
+  }
+};
+
+// (re)allocates an uncached, zeroed device array once a level needs more elements than it holds
+static int grow_uncached(ia_ctx *c, void **p, int *have, int64_t want, size_t elem_bytes) {
+  if (*have >= want) return IA_OK;
+  HIP_TRY(hipStreamSynchronize(c->st));
+  if (*p) hipFree(*p);
+  *p = nullptr;
+  *have = 0;
+  HIP_TRY(hipExtMallocWithFlags(p, (size_t)want * elem_bytes, hipDeviceMallocUncached));
+  HIP_TRY(hipMemset(*p, 0, (size_t)want * elem_bytes));
+  HIP_TRY(hipDeviceSynchronize());
+  *have = (int)want;
+  return IA_OK;
+}
+
+struct QBufs {  // the query buffers of one step
+  double *q64, *qn2;
+  float4 *qinfo;
+};
+
+// One owner-computes sharded step (exchange = 2, ia_internal.h XOLayout): every local owner (a
+// rank: its own job; emulated: job j = owner j, each at its own tile-aligned offset) gathers its
+// queries (K2p) and sorts them into every rank's area (K2s); this process's shard scans (K3p) run
+// for all owners' queries and push their records to the owners; each local owner's fused merge
+// (K4) runs over W nch records per query.  The emulated launches are exactly the ranks'
+// launches, one after the other.
+struct OwnerStep {
+  unsigned seq;
+  char *loc;    // this process's area of the step's parity
+  StepDesc s1;  // one owner's step
+  int Mpj;      // one owner's padded queries
+  bool ink;     // owners whose step fits one launch's query tiles skip K2s: K2p publishes the unsorted
+                // queries and each K3p block sorts its owner's queries itself (XOPub)
+  int QTs;      // tiles per owner in this step's layout
+  int Mrec, nqb, nch;
+};
+
+// ---- phase 4: the steps of one level --------------------------------------------------------
+struct LevelRun {
+  ia_ctx *c;
+  const LevelPlan &P;
+  const LevelGeo &g;
+  const LevelInputs &in;
+  StampSlots &stamps;
+  PipelineLink &link;
+  ScanTally tally;
+  double ufac;
+  MergeArgs ma;                     // the level's merge arguments; per shard: its records,
+  std::vector<MergeArgs> mas;       // decomposition, DB positions (and table / boxes when pruned)
+  std::vector<int64_t> shard_rows;  // real DB rows in each shard (unpruned flops)
+  bool chain = false;               // fused K4(t) + K2(t + 1) launches, handoff-chained (option "fuse_gather")
+  ChainReservation &chain_res;
+  bool fsort = false;               // their gathers may also sort the next step (option "fuse_sort")
+  int64_t gathered = -1;            // the step whose gather the previous fused launch ran
+  bool gsort = false;               // ... and that launch also sorted it (no K2s, no in-scan sort)
+  int64_t n_gm = 0;                 // sampled steps (gather / merge brackets)
+  double gq_bytes = 0., gather_bytes_timed = 0.;
+
+  LevelRun(ia_ctx *ctx, const LevelPlan &plan, const LevelInputs &inputs, StampSlots &s, PipelineLink &l, ChainReservation &r,
+           double uf)
+      : c(ctx), P(plan), g(plan.g), in(inputs), stamps(s), link(l), tally{ctx, plan.stride}, ufac(uf), chain_res(r) {}
+
+  void init_merge_args() {
+    const bool prune = P.prune, use_h = P.use_h;
+    ma.db64 = c->db64.as<double>();
+    ma.rec = c->rec.as<float4>();
+    ma.recT = c->recT.as<float>();
+    ma.q64 = c->q64.as<double>();
+    ma.qn2 = c->qn2.as<double>();
+    ma.Rbits = c->Rbits.as<unsigned>();
+    ma.nwg = g.nwg;
+    ma.tpw = g.tiles_per_wg;
+    ma.pos0 = g.tile0 * IA_TILE;
+    ma.pos_end = g.tile1 * IA_TILE;
+    ma.NT = g.n_tiles;
+    ma.NA = (int)g.NA;
+    ma.pos2row = g.pos2row;
+    ma.rr = prune ? 1 : 0;
+    ma.qinfo = prune ? c->qinfo.as<float4>() : nullptr;
+    ma.boxes = prune ? c->boxes.as<float4>() : nullptr;
+    ma.ufac = ufac;
+    ma.img_rows = 0;  // (exact rows from the A images: git history only, option "row_source")
+    ma.eps_c = use_h ? ia_eps_c_h(g.KS, prune || c->k3_variant == 1) : ia_eps_c(P.DP);
+    ma.eps_a = use_h ? ia_eps_a_h() : 0.;
+    mas.assign(P.shards.size(), ma);
+    shard_rows.assign(P.shards.size(), 0);
+    for (size_t i = 0; i < P.shards.size(); i++) {
+      const Shard &x = P.shards[i];
+      MergeArgs &m = mas[i];
+      m.rec = c->rec.as<float4>() + i * P.rec_stride;
+      m.recT = c->recT.as<float>() + i * P.rec_stride;
+      m.nwg = x.nwg;
+      m.tpw = x.tpw;
+      m.pos0 = x.t0 * IA_TILE;
+      m.pos_end = x.t1 * IA_TILE;
+      if (prune) {
+        m.pos2row = g.pos2row + (size_t)x.t0 * IA_TILE;
+        m.boxes = c->boxes.as<float4>() + 2 * (size_t)x.t0;
+        m.NT = x.t1 - x.t0;
+      }
+      for (int t = x.t0; t < x.t1 && !prune; t++) {
+        const int64_t tr = ia_tile_perm(t, g.n_tiles);
+        shard_rows[i] += std::min<int64_t>(IA_TILE, (g.NA - tr + g.n_tiles - 1) / g.n_tiles);
+      }
+    }
+    // algorithmic bytes of one query's gather (K2h / K2p): its 55*ch features read, (K2p) the 12
+    // causal coherence candidates' fp64 rows for U, the fp64 row + MFMA fragments + |q'|^2 (+ K2p's
+    // pruning record) written
+    gq_bytes = 55.0 * g.ch * 8 + (prune ? 12.0 * ia_db64_stride(g.ch) * 8 : 0.) + g.D * 8.0 +
+               (use_h ? 16.0 * g.KS * 4 : P.DP * 4.0) + 8.0 + (prune ? 48.0 : 0.);
+  }
+
+  // Fused K4(t) + K2p(t + 1) (option "fuse_gather", ia_kernels.hip k_merge_gather): unsharded
+  // pruned levels (<= 256 records per query: one launch's chunks, or nch <= 256 of a wide step's
+  // 2-D launch), batched jobs with one handoff row set per job, and owner-computes steps (each
+  // local owner's merge + its next gather, which publishes); the query buffers alternate by step
+  // parity.  (Unpruned levels - K2h fused, option "fuse_unpruned" - measured slower: their longer
+  // fused launches delay the pipelined finest level's scans, and cfg5's batched 512^2 steps lose
+  // 1-2 %.)  A level chains only while the process-wide chained-wave budget (g_chain_waves) has
+  // room for its widest launch: at most Mpad + J waves (merges, entering rows, pads).  Owner-
+  // computes levels take the same reservation: their fused launches chain rows like any other
+  // (and wait for peers' records besides, which never depend on a chained wave of this process).
+  int init_chain() {
+    static_assert(IA_NWG_H <= 4 * IA_WAVE, "k_merge_gather reads 4 records per lane");
+    const int J = P.J;
+    chain = c->fuse_gather && P.use_h && g.ch == 1 && g.bw >= 3 && (P.prune || c->fuse_unpruned) &&
+            ((!P.multi && !P.xo && mas[0].nwg <= 4 * IA_WAVE) || (P.xo && P.prune));
+    if (chain && !chain_res.take((int)(P.Mpad_max + J) + (P.xo ? 1 : 0), c->chain_budget)) chain = false;
+    if (chain) {
+      int rc;  // handoff slots per row of every job (local owner); key slots of the gathers' sort
+      if ((rc = grow_uncached(c, (void **)&c->hand, &c->hand_rows, g.bh * J, sizeof(HandSlot))) ||
+          (rc = grow_uncached(c, (void **)&c->kslot, &c->kslot_n, P.Mpad_max, 8)) || (rc = c->xerr.ensure(4)))
+        return rc;
+      HIP_TRY(hipMemsetAsync(c->xerr.p, 0, 4, c->st));
+    }
+    // (the gathers' sort waits for every wave of its launch: only while all chained waves in flight
+    // fit the resident slots, half the budget)
+    fsort = chain && P.prune && !P.xo && (c->fuse_sort == 1 || (c->fuse_sort == 2 && P.Mtmax >= IA_FUSE_SORT_MINQ)) &&
+            g_chain_waves.load() <= c->chain_budget / 2;
+    const int64_t n_timed = P.stride ? (P.T + P.stride - 1) / P.stride : 0;
+    for (auto *v : {&c->evs, &c->evg, &c->evm})
+      if ((int64_t)v->size() < 2 * n_timed) {
+        size_t old = v->size();
+        v->resize(2 * n_timed);
+        for (size_t i = old; i < v->size(); i++) hipEventCreate(&(*v)[i]);
+      }
+    return IA_OK;
+  }
+
+  // query buffers of step t (chain: parity half t & 1)
+  QBufs qhalf(int64_t t) const {
+    const size_t h = chain && (t & 1) ? 1 : 0;
+    return QBufs{c->q64.as<double>() + h * P.Mpad_max * g.D, c->qn2.as<double>() + h * P.Mpad_max,
+                 P.prune ? c->qinfo.as<float4>() + h * 3 * P.Mpad_max : nullptr};
+  }
+  // a step's merge also runs the next step's gather; not on sampled steps (their K2 / K4 brackets)
+  bool fuses_next(int64_t t) const {
+    return chain && t + 1 < P.T && !(P.stride && (t % P.stride == 0 || (t + 1) % P.stride == 0));
+  }
+  // algorithmic bytes of a pruned launch besides its DB tiles
+  double scan_fixed_bytes(double tile_visits, double query_slots, double rec_bytes) const {
+    return tile_visits * 32 + query_slots * (16.0 * 16 * g.KS + 48) + rec_bytes;
+  }
+  const char *shard_db(const Shard &x) const { return (const char *)c->db.p + (size_t)(x.t0 - g.tile0) * P.tile_bytes; }
+
+  // the gather of step sn fused into a merge: outputs at query q0n of the step's buffers, the
+  // handoff rows of local job jl
+  NextStep next_step(const StepDesc &sn, int jl, size_t q0n) {
+    NextStep nx{};
+    nx.sn = sn;
+    const QBufs q = qhalf(sn.t);
+    nx.q64 = q.q64 + q0n * g.D;
+    nx.qn2 = q.qn2 + q0n;
+    nx.qinfo = q.qinfo ? q.qinfo + 3 * q0n : nullptr;
+    nx.qf = (char *)c->qf.p + q0n * P.db_row_bytes;
+    nx.mu = c->mu.as<double>();
+    nx.basis = c->pr_basis.as<double>();
+    nx.ufac = ufac;
+    nx.hand = c->hand + (size_t)jl * g.bh;
+    nx.seq = ++c->hseq;
+    nx.err = c->xerr.as<unsigned>();
+    nx.timeout_ticks = IA_WAIT_TICKS;
+    nx.prefetch = c->prefetch_next;
+    nx.early = c->early_gather;
+    return nx;
+  }
+
+  int step(int64_t t) {
     StepDesc sd;
     sd.t = (int)t;
-    sd.J = J;
+    sd.J = P.J;
     ia_wavefront_step(g.bh, g.bw, t, &sd.r0, &sd.M);
-    if (sd.M <= 0) {  // levels narrower than 3 columns have empty steps
-      ord_n = 0;
-      continue;
-    }
-    const int Mt = J * sd.M;  // queries of this step over all jobs
-    sd.Mpad = (Mt + IA_TILE - 1) / IA_TILE * IA_TILE;
-    const bool timed_gm = stride && t % stride == 0;
+    if (sd.M <= 0) return IA_OK;  // levels narrower than 3 columns have empty steps
+    const int Mt = P.J * sd.M;    // queries of this step over all jobs
+    sd.Mpad = (int)tile_pad(Mt);
+    const bool timed_gm = P.stride && t % P.stride == 0;
     if (timed_gm) {
       hipEventRecord(c->evg[2 * n_gm], c->st);
       gather_bytes_timed += gq_bytes * Mt;
     }
-    if (xo) {
-      // ---- owner-computes sharded step (exchange = 2, ia_internal.h XOLayout): every local owner
-      // (a rank: its own job; emulated: job j = owner j, each at its own tile-aligned offset)
-      // gathers its queries (K2p) and sorts them into every rank's area (K2s); this process's
-      // shard scans (K3p) run for all owners' queries and push their records to the owners; each
-      // local owner's fused merge (K4) runs over W nch records per query.  The emulated launches
-      // are exactly the ranks' launches, one after the other.
-      const unsigned seq = ++c->xseq;
-      auto area_s = [&](int p, unsigned sq) -> char * {  // parity base of rank p's area for step seq sq
-        return (char *)(sharded ? (void *)c->xpeer[p] : c->xbuf) + ia_xslots_bytes(Wsh) + (size_t)(sq & 1u) * XOLayout::PARITY;
-      };
-      auto area = [&](int p) -> char * { return area_s(p, seq); };
-      char *loc = area(sharded ? c->rank : 0);
-      const int Mpj = (sd.M + IA_TILE - 1) / IA_TILE * IA_TILE;  // one owner's padded queries
-      // owners whose step fits one launch's query tiles skip K2s: K2p publishes the unsorted
-      // queries and each K3p block sorts its owner's queries itself (XOPub)
-      const bool ink = Mpj <= ia_k3h_qtmax(g.KS) * IA_TILE && !c->xo_presort;
-      const int QTs = ink ? Mpj / IA_TILE : xo_QTs;  // tiles per owner in this step's layout
-      const int Mrec = Wsh * QTs * IA_TILE;
-      StepDesc s1 = sd;
-      s1.J = 1;
-      s1.Mpad = Mpj;
-      auto owner_of = [&](int jl) { return sharded ? c->rank : jl; };
-      double *q64t, *qn2t;
-      float4 *qinfot;
-      qhalf(t, q64t, qn2t, qinfot);
-      for (int jl = 0; jl < J; jl++) {
-        const JobSet one{jp[jl], c->jobs.as<JobPtrs>() + jl, 1};
-        const size_t q0 = (size_t)jl * Mpj;
-        if (chain && gathered == t) {  // K2p (+ publish) ran in the previous step's fused merge
-          if (!ink)
-            ia_launch_query_sort_xo_owner(c, g, qinfot + 3 * q0, (char *)c->qf.p + q0 * db_row_bytes, sd, owner_of(jl),
-                                          QTs, seq, sharded ? Wsh : 1, area);
-          continue;
-        }
-        XOPub xp{};
-        if (ink) {
-          xp.W = sharded ? Wsh : 1;
-          for (int p = 0; p < xp.W; p++) xp.area[p] = area(p);
-          xp.slot0 = owner_of(jl) * Mpj;
-          xp.seq = seq;
-        }
-        ia_launch_gather_p(g, s1, Bim, one, c->mu.as<double>(), q64t + q0 * g.D, qn2t + q0,
-                           (char *)c->qf.p + q0 * db_row_bytes, c->db64.as<double>(), c->pr_basis.as<double>(), ufac,
-                           qinfot + 3 * q0, Aim, ma.img_rows, c->st, &xp);
-        if (ink) continue;
-        ia_launch_query_sort_xo_owner(c, g, qinfot + 3 * q0, (char *)c->qf.p + q0 * db_row_bytes, sd, owner_of(jl), QTs,
-                                      seq, sharded ? Wsh : 1, area);
-      }
+    const QBufs q = qhalf(t);
+    int rc;
+    if (P.xo) {
+      const OwnerStep os = owner_step(sd);
+      owner_gather(sd, os, q);
       if (timed_gm) hipEventRecord(c->evg[2 * n_gm + 1], c->st);
-      const int nqb = ink ? Wsh : Wsh * xo_bpj;
-      const bool timed = stride && t % stride == 0;
-      if (timed) hipEventRecord(c->evs[2 * n_rec], c->st);
-      // one chunk count for every shard (the owners' merges index records as shard * nch + chunk
-      // and map a chunk back to its tiles with it): from the smallest shard, which every rank
-      // computes alike (shards differ by at most one tile, ia_shard_off)
-      int nch = std::max(1, std::min((int)(g.n_tiles / Wsh), IA_NWG_H / nqb));
-      if (nch >= 64) nch &= ~7;
-      for (size_t i = 0; i < shards.size(); i++) {
-        const Shard &x = shards[i];
-        const int n = x.t1 - x.t0;
-        if ((n + nch - 1) / nch > IA_K3P_MAXK_LDS || (int64_t)Wsh * nch * Mrec > IA_XO_MAXREC)
-          return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2: shard too large for the pruned scan's chunks");
-        XOScan xs{};
-        for (int p = 0; p < Wsh; p++) xs.area[p] = sharded ? area(p) : loc;
-        xs.flag = reinterpret_cast<const unsigned *>(loc + (ink ? XOLayout::QSEQ : XOLayout::FLAG));
-        xs.inv = c->xo_inv.as<int>();
-        xs.on = 1;
-        xs.s = sharded ? c->rank : (int)i;
-        xs.bpj = ink ? 1 : xo_bpj;
-        xs.Mrec = Mrec;
-        xs.seq = seq;
-        xs.err = c->xerr.as<unsigned>();
-        xs.timeout_ticks = 2000000000LL;  // 20 s of the 100 MHz s_memrealtime clock
-        const char *dbp = (const char *)c->db.p + (size_t)(x.t0 - g.tile0) * tile_bytes;
-        const int kv = c->k3p_variant;
-        // the in-kernel-sort variant (ink: 20 / 22 / 24) or its presorted form (21 / 25)
-        const int k3x = ink ? (kv == 21 ? 20 : kv == 25 ? 24 : kv) : (kv == 25 ? 25 : 21);
-        {
-            if (ia_launch_k3p(ink ? QTs : xo_QTx, dbp, loc + XOLayout::FRAG, reinterpret_cast<const float4 *>(loc + XOLayout::INFO),
-                      mas[i].boxes, mas[i].pos2row, n, 0, sd.M, ink ? Mpj : Mrec, nch, nullptr, nullptr,
-                      c->pairs.as<unsigned long long>() + (timed ? IA_NWG_H : 0),
-                      c->pairs.as<unsigned long long>() + (timed ? 3 : 2) * IA_NWG_H, k3x, sd.t,
-                      reinterpret_cast<const int *>(loc + XOLayout::ORD), 0, sd.r0, nullptr,
-                      reinterpret_cast<const float4 *>(loc + XOLayout::TBOX), c->tnorm.as<float>() + x.t0, c->st, nqb,
-                      Wsh * QTs, &xs, k3_stamp(), c->rec_wt)) return fail(IA_EINVAL, "pruned scan: no kernel instance for k3p_variant");
-          }
-        pairs_full += (double)n * Wsh * QTs;
-        tiles_full += (double)n * nqb;
-        dist_launches++;
-        bytes_all_fixed += (double)n * nqb * 32 + (double)Mrec * (16.0 * 16 * g.KS + 48) + (double)Mrec * nch * 24;
-        db_cap_all += (double)n * tile_bytes;
-        if (timed) {
-          launches_timed++;
-          bytes_timed_fixed += (double)n * nqb * 32 + (double)Mrec * (16.0 * 16 * g.KS + 48) + (double)Mrec * nch * 24;
-        }
-      }
-      if (timed) hipEventRecord(c->evs[2 * n_rec++ + 1], c->st);
+      if ((rc = owner_scan(sd, os))) return rc;
       if (timed_gm) hipEventRecord(c->evm[2 * n_gm], c->st);
-      // the next step's layout (fused merge + gather: each owner publishes its next queries)
-      const bool fuse_next = chain && t + 1 < T && !(stride && (t % stride == 0 || (t + 1) % stride == 0));
-      StepDesc sn{};
-      int Mpj_n = 0;
-      bool ink_n = false;
-      double *q64n = nullptr, *qn2n = nullptr;
-      float4 *qinfon = nullptr;
-      if (fuse_next) {
-        if ((rc = wait_dep(t + 1))) return rc;
-        sn.t = (int)(t + 1);
-        sn.J = 1;
-        ia_wavefront_step(g.bh, g.bw, t + 1, &sn.r0, &sn.M);
-        Mpj_n = (sn.M + IA_TILE - 1) / IA_TILE * IA_TILE;
-        sn.Mpad = Mpj_n;
-        ink_n = Mpj_n <= ia_k3h_qtmax(g.KS) * IA_TILE && !c->xo_presort;
-        qhalf(t + 1, q64n, qn2n, qinfon);
-      }
-      for (int jl = 0; jl < J; jl++) {
-        const JobSet one{jp[jl], c->jobs.as<JobPtrs>() + jl, 1};
-        const size_t q0 = (size_t)jl * Mpj;
-        MergeArgs mx = ma;
-        mx.q64 = q64t + q0 * g.D;
-        mx.qn2 = qn2t + q0;
-        mx.qinfo = qinfot + 3 * q0;
-        mx.rec = reinterpret_cast<const float4 *>(loc + XOLayout::REC);
-        mx.xo_rts = reinterpret_cast<const unsigned long long *>(loc + XOLayout::RTS);
-        mx.nwg = Wsh * nch;
-        mx.rr = 1;
-        mx.NT = g.n_tiles;
-        mx.boxes = c->boxes.as<float4>();
-        mx.pos2row = g.pos2row;
-        mx.xo_inv = c->xo_inv.as<int>();
-        mx.xo_W = Wsh;
-        mx.xo_nch = nch;
-        mx.xo_Mrec = Mrec;
-        mx.xo_o0 = owner_of(jl);
-        mx.xo_M = sd.M;
-        mx.xo_QTs = QTs;
-        mx.xo_seq = seq;
-        mx.xo_err = c->xerr.as<unsigned>();
-        mx.xo_timeout = 2000000000LL;
-        mx.stamp = mg_stamp();
-        if (!fuse_next) {
-          ia_launch_merge(g, s1, Aim, mx, c->win.as<Winner>(), one, true, c->st);
+      if ((rc = owner_merge(sd, os, q))) return rc;
+    } else {
+      gather(sd, q);
+      if (timed_gm) hipEventRecord(c->evg[2 * n_gm + 1], c->st);
+      if ((rc = scan(sd, q))) return rc;
+      if (timed_gm) hipEventRecord(c->evm[2 * n_gm], c->st);
+      if ((rc = merge(sd))) return rc;
+    }
+    if (timed_gm) hipEventRecord(c->evm[2 * n_gm++ + 1], c->st);
+    return IA_OK;
+  }
+
+  // ---- one-rank, all-gather and peer-write steps
+  void gather(const StepDesc &sd, const QBufs &q) {
+    if (chain) {
+      mas[0].q64 = q.q64;
+      mas[0].qn2 = q.qn2;
+      mas[0].qinfo = q.qinfo;
+    }
+    if (chain && gathered == sd.t) return;  // this step's gather ran in the previous step's fused merge
+    if (P.prune)
+      ia_launch_gather_p(g, sd, in.Bim, in.jobs(), c->mu.as<double>(), q.q64, q.qn2, c->qf.p, c->db64.as<double>(),
+                         c->pr_basis.as<double>(), ufac, q.qinfo, in.Aim, c->st);
+    else if (P.use_h)
+      ia_launch_gather_h(g, sd, in.Bim, in.jobs(), c->mu.as<double>(), q.q64, q.qn2, c->qf.p, c->st);
+    else
+      ia_launch_gather(g, sd, in.Bim, in.jobs(), c->mu.as<double>(), c->q64.as<double>(), c->qn2.as<double>(),
+                       c->qf.as<float>(), c->st);
+  }
+
+  int scan(const StepDesc &sd, const QBufs &q) {
+    const bool prune = P.prune;
+    const int Mt = P.J * sd.M;
+    // The pruned scan takes its queries presorted (one K2s launch per step) when the option names
+    // a presorted form, when the step is wider than the in-kernel sort (512 queries), when it is
+    // wider than one launch's query tiles and its blocks run as one launch (k3p_blocks: one K2s
+    // launch instead of a second scan launch), or when the previous launch's gathers sorted it
+    // (then without K2s, the tile boxes taken from the slice)
+    const bool wide = sd.Mpad > 512 || (c->k3p_blocks && sd.Mpad > P.qtmax * IA_TILE);
+    const bool gsorted = fsort && gathered == sd.t && gsort;
+    const bool presorted = prune && (c->k3p_variant == 21 || c->k3p_variant == 25 || wide || gsorted);
+    if (presorted && !gsorted)
+      ia_launch_query_sort(q.qinfo, c->qf.p, sd.Mpad, g.KS, c->qs_order.as<int>(), c->qs_info.as<float4>(), c->qs_frag.p,
+                           c->qs_tbox.as<float4>(), c->st);
+    if (P.ns <= 0) return IA_OK;
+    const int qtt = sd.Mpad / IA_TILE, nqb = (qtt + P.qtmax - 1) / P.qtmax;
+    tally.begin_step(sd.t);
+    for (size_t i = 0; i < P.shards.size(); i++) {
+      const Shard &x = P.shards[i];
+      MergeArgs &m = mas[i];
+      const int n = x.t1 - x.t0;
+      const char *dbp = shard_db(x);
+      m.nwg = x.nwg;
+      K3pLaunch k{};
+      k.db = dbp;
+      k.NT = n;
+      k.qf = presorted ? c->qs_frag.p : c->qf.p;
+      k.qinfo = presorted ? c->qs_info.as<float4>() : q.qinfo;
+      k.order = presorted ? c->qs_order.as<int>() : nullptr;
+      k.tbox = presorted && !gsorted ? c->qs_tbox.as<float4>() : nullptr;
+      k.boxes = m.boxes;
+      k.pos2row = m.pos2row;
+      k.tnorm = prune ? c->tnorm.as<float>() + x.t0 : nullptr;
+      k.M = Mt;
+      k.Mpad = sd.Mpad;
+      k.rec = (float4 *)m.rec;
+      k.recT = (float *)m.recT;
+      k.pairs = tally.pairs();
+      k.tiles = tally.tiles();
+      k.step = sd.t;
+      k.r0 = sd.r0;
+      k.rec_wt = c->rec_wt;
+      if (presorted && nqb > 1 && c->k3p_blocks) {
+        // one launch for all query blocks (option "k3p_blocks"): nqb blocks x nch DB chunks of
+        // the shard, nch a multiple of 8 (the blocks of a chunk on one XCD) when that loses
+        // little; records per query = nch, the merge's chunk count for this step
+        int nch = std::max(1, std::min(n, IA_NWG_H / nqb));
+        if (nch >= 64) nch &= ~7;
+        if ((n + nch - 1) / nch <= IA_K3P_MAXK_LDS) {
+          k.qt = (qtt + nqb - 1) / nqb;
+          k.nwg = nch;
+          k.nqb = nqb;
+          k.qt_end = qtt;
+          k.stamp = stamps.k3();
+          if (ia_launch_k3p(k, c->k3p_variant, true, c->st)) return fail(IA_EINVAL, "pruned scan: no kernel instance for k3p_variant");
+          m.nwg = nch;
+          tally.add((double)n * qtt, (double)n * nqb, 0., true, scan_fixed_bytes((double)n * nqb, sd.Mpad, (double)Mt * nch * 20),
+                    (double)n * P.tile_bytes);
           continue;
         }
-        const size_t q0n = (size_t)jl * Mpj_n;
-        NextStep nx{};
-        nx.sn = sn;
-        nx.q64 = q64n + q0n * g.D;
-        nx.qn2 = qn2n + q0n;
-        nx.qinfo = qinfon + 3 * q0n;
-        nx.qf = (char *)c->qf.p + q0n * db_row_bytes;
-        nx.mu = c->mu.as<double>();
-        nx.basis = c->pr_basis.as<double>();
-        nx.ufac = ufac;
-        nx.hand = c->hand + (size_t)jl * g.bh;
-        nx.seq = ++c->hseq;
-        nx.err = c->xerr.as<unsigned>();
-        nx.timeout_ticks = 2000000000LL;
-        nx.prefetch = c->prefetch_next;
-        nx.early = c->early_gather;
-        if (ink_n) {  // the next step's queries go straight to every rank's area (else its K2s sorts them)
-          nx.xp.W = sharded ? Wsh : 1;
-          for (int p = 0; p < nx.xp.W; p++) nx.xp.area[p] = area_s(p, seq + 1);
-          nx.xp.slot0 = owner_of(jl) * Mpj_n;
-          nx.xp.seq = seq + 1;
-          if (sharded && c->xo_wait && jl == J - 1) {  // ranks: wait here for every owner's next queries
-            nx.wait_seq = reinterpret_cast<const unsigned *>(area_s(c->rank, seq + 1) + XOLayout::QSEQ);
-            nx.wait_n = Wsh * Mpj_n;
-          }
-        }
-        ia_launch_merge_gather(g, s1, Aim, mx, one, Bim, nx, true, c->st);
       }
-      if (fuse_next) gathered = t + 1;
-      if (timed_gm) hipEventRecord(c->evm[2 * n_gm++ + 1], c->st);
-      continue;
-    }
-    double *q64t, *qn2t;
-    float4 *qinfot;
-    qhalf(t, q64t, qn2t, qinfot);
-    if (chain) {
-      mas[0].q64 = q64t;
-      mas[0].qn2 = qn2t;
-      mas[0].qinfo = qinfot;
-    }
-    if (chain && gathered == t)
-      ;  // this step's gather ran in the previous step's fused merge
-    else if (prune)
-      ia_launch_gather_p(g, sd, Bim, djobs, c->mu.as<double>(), q64t, qn2t, c->qf.p, c->db64.as<double>(),
-                         c->pr_basis.as<double>(), ufac, qinfot, Aim, ma.img_rows, c->st);
-    else if (use_h)
-      ia_launch_gather_h(g, sd, Bim, djobs, c->mu.as<double>(), q64t, qn2t, c->qf.p, c->st);
-    else
-      ia_launch_gather(g, sd, Bim, djobs, c->mu.as<double>(), c->q64.as<double>(), c->qn2.as<double>(), c->qf.as<float>(),
-                       c->st);
-    if (timed_gm) hipEventRecord(c->evg[2 * n_gm + 1], c->st);
-    // pruned scan: queries sorted once per step (K2s) when the step is wider than the in-kernel
-    // sort of v6/v7 (512) or variant 11 is selected
-    // (variants 11, 12: presorted; 7, 13: in-kernel sort up to 512 queries, presorted v11 / v12 above)
-    const int kv = c->k3p_variant;
-    // steps wider than one launch's query tiles take the presorted form too when their blocks
-    // run as one launch (k3p_blocks): one K2s launch instead of a second scan launch
-    const bool wide = sd.Mpad > 512 || (c->k3p_blocks && sd.Mpad > qtmax * IA_TILE);
-    // sorted by the previous launch's gathers: the presorted form of the variant, no K2s
-    const bool gsorted = fsort && gathered == t && gsort;
-    // wide steps: the presorted form of the variant - under 24 that is 25, the two-pass form
-    // (round 6, on the trimmed stream: cfg4 6.66 -> 6.91 M px/s against 21's whole tiles; round 4's
-    // kernels had it the other way), under 20 / 22 it is 21
-    const int k3v = (kv == 21 || kv == 25) ? kv : (prune && (wide || gsorted) ? (kv == 24 ? 25 : 21) : kv);
-    const bool presorted = k3v == 21 || k3v == 25;
-    const float4 *tboxp = gsorted ? nullptr : c->qs_tbox.as<float4>();  // nullptr: boxes from the slice
-    if (prune && presorted && !gsorted)
-      ia_launch_query_sort(qinfot, c->qf.p, sd.Mpad, g.KS, c->qs_order.as<int>(), c->qs_info.as<float4>(),
-                           c->qs_frag.p, c->qs_tbox.as<float4>(), c->st);
-    if (ns > 0) {
-      const int qtt = sd.Mpad / IA_TILE, nqb = (qtt + qtmax - 1) / qtmax;
-      const bool timed = stride && t % stride == 0;
-      if (timed) hipEventRecord(c->evs[2 * n_rec], c->st);
-      for (size_t i = 0; i < shards.size(); i++) {
-        const Shard &x = shards[i];
-        MergeArgs &m = mas[i];
-        const int n = x.t1 - x.t0;
-        const char *dbp = (const char *)c->db.p + (size_t)(x.t0 - g.tile0) * tile_bytes;
-        m.nwg = x.nwg;
-        if (prune && presorted && nqb > 1 && c->k3p_blocks) {
-          // one launch for all query blocks (option "k3p_blocks"): nqb blocks x nch DB chunks of
-          // the shard, nch a multiple of 8 (the blocks of a chunk on one XCD) when that loses
-          // little; records per query = nch, the merge's chunk count for this step
-          int nch = std::max(1, std::min(n, IA_NWG_H / nqb));
-          if (nch >= 64) nch &= ~7;
-          if ((n + nch - 1) / nch <= IA_K3P_MAXK_LDS) {
-            const int qtb = (qtt + nqb - 1) / nqb;
-            const float *tn = c->tnorm.as<float>() + x.t0;
-            {
-            if (ia_launch_k3p(qtb, dbp, c->qs_frag.p, c->qs_info.as<float4>(), m.boxes, m.pos2row, n, 0, Mt, sd.Mpad, nch,
-                          (float4 *)m.rec, (float *)m.recT, c->pairs.as<unsigned long long>() + (timed ? IA_NWG_H : 0),
-                          c->pairs.as<unsigned long long>() + (timed ? 3 : 2) * IA_NWG_H, k3v, sd.t, c->qs_order.as<int>(),
-                          0, sd.r0, nullptr, tboxp, tn, c->st, nqb, qtt, nullptr, k3_stamp(), c->rec_wt)) return fail(IA_EINVAL, "pruned scan: no kernel instance for k3p_variant");
-          }
-            m.nwg = nch;
-            pairs_full += (double)n * qtt;
-            tiles_full += (double)n * nqb;
-            dist_launches++;
-            bytes_all_fixed += (double)n * nqb * 32 + (double)sd.Mpad * (16.0 * 16 * g.KS + 48) + (double)Mt * nch * 20;
-            db_cap_all += (double)n * tile_bytes;
-            if (timed) {
-              launches_timed++;
-              bytes_timed_fixed += (double)n * nqb * 32 + (double)sd.Mpad * (16.0 * 16 * g.KS + 48) + (double)Mt * nch * 20;
-            }
-            continue;
-          }
+      int qt0 = 0;
+      for (int b = 0; b < nqb; b++) {  // one launch per query block
+        const int qt = qtt / nqb + (b < qtt % nqb ? 1 : 0);
+        if (prune) {
+          k.qt = qt;
+          k.qt0 = qt0;
+          k.nwg = x.nwg;
+          k.stamp = stamps.k3();
+          if (ia_launch_k3p(k, c->k3p_variant, presorted, c->st)) return fail(IA_EINVAL, "pruned scan: no kernel instance for k3p_variant");
+        } else if (P.use_h) {
+          ia_launch_k3h(g.KS, qt, dbp, c->qf.p, n, x.tpw, qt0, Mt, x.nwg, m.pos0, g.n_tiles, (float4 *)m.rec, (float *)m.recT, c->st);
+        } else {
+          ia_launch_k3(g.KH, qt, (const float4 *)dbp, c->qf.as<float4>(), n, x.tpw, qt0, Mt, x.nwg, m.pos0, g.n_tiles,
+                       (float4 *)m.rec, (float *)m.recT, c->st);
         }
-        int qt0 = 0;
-        for (int b = 0; b < nqb; b++) {
-          const int qt = qtt / nqb + (b < qtt % nqb ? 1 : 0);
-          const float *tn = prune ? c->tnorm.as<float>() + x.t0 : nullptr;
-          if (prune && presorted)
-            {
-            if (ia_launch_k3p(qt, dbp, c->qs_frag.p, c->qs_info.as<float4>(), m.boxes, m.pos2row, n, qt0, Mt, sd.Mpad, x.nwg,
-                          (float4 *)m.rec, (float *)m.recT, c->pairs.as<unsigned long long>() + (timed ? IA_NWG_H : 0),
-                          c->pairs.as<unsigned long long>() + (timed ? 3 : 2) * IA_NWG_H, k3v, sd.t,
-                          c->qs_order.as<int>(), 0, sd.r0, nullptr, tboxp, tn, c->st, 1, 0, nullptr, k3_stamp(), c->rec_wt)) return fail(IA_EINVAL, "pruned scan: no kernel instance for k3p_variant");
-          }
-          else if (prune)
-            {
-            if (ia_launch_k3p(qt, dbp, c->qf.p, qinfot, m.boxes, m.pos2row, n, qt0, Mt, sd.Mpad, x.nwg,
-                          (float4 *)m.rec, (float *)m.recT, c->pairs.as<unsigned long long>() + (timed ? IA_NWG_H : 0),
-                          c->pairs.as<unsigned long long>() + (timed ? 3 : 2) * IA_NWG_H,
-                          k3v, sd.t, c->ord.as<int>() + (sd.t & 1 ? 0 : 4096), ord_n, sd.r0,
-                          c->ord.as<int>() + (sd.t & 1 ? 4096 : 0), nullptr, tn, c->st, 1, 0, nullptr, k3_stamp(), c->rec_wt)) return fail(IA_EINVAL, "pruned scan: no kernel instance for k3p_variant");
-          }
-          else if (use_h)
-            ia_launch_k3h(g.KS, qt, dbp, c->qf.p, n, x.tpw, qt0, Mt, x.nwg, m.pos0, g.n_tiles, (float4 *)m.rec,
-                          (float *)m.recT, c->k3_variant, c->st);
-          else
-            ia_launch_k3(g.KH, qt, (const float4 *)dbp, c->qf.as<float4>(), n, x.tpw, qt0, Mt, x.nwg, m.pos0, g.n_tiles,
-                         (float4 *)m.rec, (float *)m.recT, c->st);
-          const int mq = std::min(Mt, (qt0 + qt) * IA_TILE) - qt0 * IA_TILE;
-          const double fl = prune ? 0. : 2.0 * g.D * (double)shard_rows[i] * std::max(mq, 0);  // pruned: pair counters
-          dist_flops += fl;
-          pairs_full += (double)n * qt;
-          tiles_full += (double)n;
-          dist_launches++;
-          if (prune) {
-            bytes_all_fixed += (double)n * 32 + (double)sd.Mpad * (16.0 * 16 * g.KS + 48) + (double)mq * x.nwg * 20;
-            db_cap_all += (double)n * tile_bytes;
-          }
-          if (timed) {
-            flops_timed += fl;
-            launches_timed++;
-            // algorithmic bytes of a pruned launch besides its DB tiles: tile boxes, query
-            // fragments and pruning records, K3 records written
-            bytes_timed_fixed += (double)n * 32 + (double)sd.Mpad * (16.0 * 16 * g.KS + 48) + (double)mq * x.nwg * 20;
-          }
-          qt0 += qt;
-        }
+        const int mq = std::min(Mt, (qt0 + qt) * IA_TILE) - qt0 * IA_TILE;
+        const double fl = prune ? 0. : 2.0 * g.D * (double)shard_rows[i] * std::max(mq, 0);  // pruned: pair counters
+        tally.add((double)n * qt, (double)n, fl, prune, scan_fixed_bytes((double)n, sd.Mpad, (double)mq * x.nwg * 20),
+                  (double)n * P.tile_bytes);
+        qt0 += qt;
       }
-      if (timed) hipEventRecord(c->evs[2 * n_rec++ + 1], c->st);
-      ord_n = prune && J == 1 && !multi && sd.Mpad <= 4096 ? sd.M : 0;
     }
-    if (timed_gm) hipEventRecord(c->evm[2 * n_gm], c->st);
-    if (!multi && chain && t + 1 < T && !(stride && (t % stride == 0 || (t + 1) % stride == 0))) {
-      // this step's merge + the next step's gather (not on sampled steps: their K2 / K4 brackets)
-      if ((rc = wait_dep(t + 1))) return rc;  // the next step's gather reads the previous level
-      NextStep nx{};
-      nx.sn.t = (int)(t + 1);
-      nx.sn.J = J;
-      ia_wavefront_step(g.bh, g.bw, t + 1, &nx.sn.r0, &nx.sn.M);
-      nx.sn.Mpad = (J * nx.sn.M + IA_TILE - 1) / IA_TILE * IA_TILE;
-      qhalf(t + 1, nx.q64, nx.qn2, nx.qinfo);
-      nx.mu = c->mu.as<double>();
-      nx.basis = c->pr_basis.as<double>();
-      nx.qf = c->qf.p;
-      nx.ufac = ufac;
-      nx.hand = c->hand;
-      nx.seq = ++c->hseq;
-      nx.err = c->xerr.as<unsigned>();
-      nx.timeout_ticks = 2000000000LL;  // 20 s of the 100 MHz s_memrealtime clock
-      nx.prefetch = c->prefetch_next;
-      nx.early = c->early_gather;
+    tally.end_step();
+    return IA_OK;
+  }
+
+  int merge(const StepDesc &sd) {
+    const int64_t t = sd.t;
+    const int Mt = P.J * sd.M;
+    if (!P.multi && fuses_next(t)) {
+      // this step's merge + the next step's gather, which reads the previous level
+      int rc;
+      if ((rc = link.wait_dep(t + 1))) return rc;
+      StepDesc sn;
+      sn.t = (int)(t + 1);
+      sn.J = P.J;
+      ia_wavefront_step(g.bh, g.bw, t + 1, &sn.r0, &sn.M);
+      sn.Mpad = (int)tile_pad(P.J * sn.M);
+      NextStep nx = next_step(sn, 0, 0);
       // the gathers also sort step t + 1 into k_query_sort's outputs when every wave of the launch
       // can be resident at once (each gather waits for all of the step's keys): k_merge_gather
       // holds one wave per SIMD (264 VGPRs), 1,024 on the chip; 768 leaves room for the kernels of
       // concurrent (pipelined) levels, which never wait on this one
-      const int nw = J * sd.M + J + (nx.sn.Mpad - J * nx.sn.M);
+      const int nw = P.J * sd.M + P.J + (sn.Mpad - P.J * sn.M);
       const bool srt = fsort && nw <= IA_FUSE_SORT_MAXW;
       if (srt) {
         nx.kslot = c->kslot;
@@ -1643,72 +1623,242 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
         nx.sinfo = c->qs_info.as<float4>();
         nx.sfrag = c->qs_frag.p;
       }
-      mas[0].stamp = mg_stamp();
-      ia_launch_merge_gather(g, sd, Aim, mas[0], djobs, Bim, nx, prune, c->st);
+      mas[0].stamp = stamps.mg();
+      ia_launch_merge_gather(g, sd, in.Aim, mas[0], in.jobs(), in.Bim, nx, P.prune, c->st);
       gathered = t + 1;
       gsort = srt;
-    } else if (!multi) {
-      mas[0].stamp = mg_stamp();
-      ia_launch_merge(g, sd, Aim, mas[0], c->win.as<Winner>(), djobs, true, c->st);
-    } else if (xchg) {
+    } else if (!P.multi) {
+      mas[0].stamp = stamps.mg();
+      ia_launch_merge(g, sd, in.Aim, mas[0], c->win.as<Winner>(), in.jobs(), true, c->st);
+    } else if (P.xchg) {
       // one-shot peer-write exchange fused into the merge: each shard's winner goes into every
       // rank's buffer; the last launch of this process waits for all W and finishes the pixels
       XchgArgs xa;
-      for (int p = 0; p < IA_XCHG_MAXW; p++) xa.peer[p] = sharded ? c->xpeer[p] : (XSlot *)c->xbuf;
-      xa.local = sharded ? c->xpeer[c->rank] : (XSlot *)c->xbuf;
-      xa.W = Wsh;
+      for (int p = 0; p < IA_XCHG_MAXW; p++) xa.peer[p] = P.sharded ? c->xpeer[p] : (XSlot *)c->xbuf;
+      xa.local = P.sharded ? c->xpeer[c->rank] : (XSlot *)c->xbuf;
+      xa.W = P.Wsh;
       xa.seq = ++c->xseq;
       xa.err = c->xerr.as<unsigned>();
-      xa.timeout_ticks = 2000000000LL;  // 20 s of the 100 MHz s_memrealtime clock
-      for (size_t i = 0; i < shards.size(); i++) {
-        xa.rank = sharded ? c->rank : (int)i;
-        ia_launch_merge_xchg(g, sd, Aim, mas[i], xa, djobs, i + 1 == shards.size(), c->st);
+      xa.timeout_ticks = IA_WAIT_TICKS;
+      for (size_t i = 0; i < P.shards.size(); i++) {
+        xa.rank = P.sharded ? c->rank : (int)i;
+        ia_launch_merge_xchg(g, sd, in.Aim, mas[i], xa, in.jobs(), i + 1 == P.shards.size(), c->st);
       }
     } else {
       // certified per-shard winners, then the global winner (smallest exact distance, lowest row)
       // and coherence / kappa / writeback, identical on every rank
-      for (size_t i = 0; i < shards.size(); i++)
-        ia_launch_merge(g, sd, Aim, mas[i], (sharded ? c->win.as<Winner>() : c->allwin.as<Winner>() + i * Mt), djobs,
+      for (size_t i = 0; i < P.shards.size(); i++)
+        ia_launch_merge(g, sd, in.Aim, mas[i], (P.sharded ? c->win.as<Winner>() : c->allwin.as<Winner>() + i * Mt), in.jobs(),
                         false, c->st);
-      if (sharded)
+      if (P.sharded)
         NCCL_TRY(ncclAllGather(c->win.p, c->allwin.p, (size_t)Mt * sizeof(Winner), ncclUint8, c->comm, c->st));
-      ia_launch_finish(g, sd, Aim, c->db64.as<double>(), c->q64.as<double>(), c->allwin.as<Winner>(), Wsh, Mt, djobs,
+      ia_launch_finish(g, sd, in.Aim, c->db64.as<double>(), c->q64.as<double>(), c->allwin.as<Winner>(), P.Wsh, Mt, in.jobs(),
                        c->st);
     }
-    if (timed_gm) hipEventRecord(c->evm[2 * n_gm++ + 1], c->st);
+    return IA_OK;
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->lv2, c->st));
-  if (stamped) {  // per-launch device ticks: K3p launches first, then the merges
-    ia_launch_stamp_durations(c->stamp_k3.as<unsigned long long>(), (int)k3_n, IA_NWG_H, c->stamp_dur.as<unsigned long long>(),
-                              c->st, c->stamp_dur.as<unsigned long long>() + 2 * (k3_n + mg_n));
-    ia_launch_stamp_durations(c->stamp_mg.as<unsigned long long>(), (int)mg_n, mg_stride,
-                              c->stamp_dur.as<unsigned long long>() + 2 * k3_n, c->st);
-    // (the slots this level wrote are cleared by stamp_clear when the call returns)
+
+  // ---- owner-computes steps
+  int owner_of(int jl) const { return P.sharded ? c->rank : jl; }
+  char *xo_area(int p, unsigned seq) const {  // parity base of rank p's area for the step of sequence seq
+    return (char *)(P.sharded ? (void *)c->xpeer[p] : c->xbuf) + ia_xslots_bytes(P.Wsh) + (size_t)(seq & 1u) * XOLayout::PARITY;
   }
-  if (stats)
-    for (int j = 0; j < J; j++) ia_launch_reduce_stats(jp[j].pstat, NB, c->counters.as<unsigned long long>(), c->st);
-  for (int j = 0; j < J; j++) {
+  OwnerStep owner_step(const StepDesc &sd) {
+    OwnerStep os;
+    os.seq = ++c->xseq;
+    os.loc = xo_area(P.sharded ? c->rank : 0, os.seq);
+    os.Mpj = (int)tile_pad(sd.M);
+    os.ink = os.Mpj <= ia_k3h_qtmax(g.KS) * IA_TILE && !c->xo_presort;
+    os.QTs = os.ink ? os.Mpj / IA_TILE : P.xo_QTs;
+    os.Mrec = P.Wsh * os.QTs * IA_TILE;
+    os.s1 = sd;
+    os.s1.J = 1;
+    os.s1.Mpad = os.Mpj;
+    os.nqb = os.ink ? P.Wsh : P.Wsh * P.xo_bpj;
+    // one chunk count for every shard (the owners' merges index records as shard * nch + chunk
+    // and map a chunk back to its tiles with it): from the smallest shard, which every rank
+    // computes alike (shards differ by at most one tile, ia_shard_off)
+    os.nch = std::max(1, std::min((int)(g.n_tiles / P.Wsh), IA_NWG_H / os.nqb));
+    if (os.nch >= 64) os.nch &= ~7;
+    return os;
+  }
+  // owner jl's K2s: its queries sorted into every rank's area
+  void owner_sort(const StepDesc &sd, const OwnerStep &os, const QBufs &q, int jl) {
+    const size_t q0 = (size_t)jl * os.Mpj;
+    XOSort xs{};
+    xs.inv = c->xo_inv.as<int>();
+    xs.W = P.sharded ? P.Wsh : 1;
+    for (int p = 0; p < xs.W; p++) xs.area[p] = xo_area(p, os.seq);
+    xs.q0 = 0;
+    xs.Mj = sd.M;
+    xs.tile0 = owner_of(jl) * os.QTs;
+    xs.QTs = os.QTs;
+    xs.seq = os.seq;
+    ia_launch_query_sort_xo(q.qinfo + 3 * q0, (char *)c->qf.p + q0 * P.db_row_bytes, xs, c->st);
+  }
+  void owner_gather(const StepDesc &sd, const OwnerStep &os, const QBufs &q) {
+    for (int jl = 0; jl < P.J; jl++) {
+      const size_t q0 = (size_t)jl * os.Mpj;
+      if (chain && gathered == sd.t) {  // K2p (+ publish) ran in the previous step's fused merge
+        if (!os.ink) owner_sort(sd, os, q, jl);
+        continue;
+      }
+      XOPub xp{};
+      if (os.ink) {
+        xp.W = P.sharded ? P.Wsh : 1;
+        for (int p = 0; p < xp.W; p++) xp.area[p] = xo_area(p, os.seq);
+        xp.slot0 = owner_of(jl) * os.Mpj;
+        xp.seq = os.seq;
+      }
+      ia_launch_gather_p(g, os.s1, in.Bim, in.job(jl), c->mu.as<double>(), q.q64 + q0 * g.D, q.qn2 + q0,
+                         (char *)c->qf.p + q0 * P.db_row_bytes, c->db64.as<double>(), c->pr_basis.as<double>(), ufac,
+                         q.qinfo + 3 * q0, in.Aim, c->st, &xp);
+      if (!os.ink) owner_sort(sd, os, q, jl);
+    }
+  }
+  int owner_scan(const StepDesc &sd, const OwnerStep &os) {
+    const int Wsh = P.Wsh;
+    tally.begin_step(sd.t);
+    for (size_t i = 0; i < P.shards.size(); i++) {
+      const Shard &x = P.shards[i];
+      const int n = x.t1 - x.t0;
+      if ((n + os.nch - 1) / os.nch > IA_K3P_MAXK_LDS || (int64_t)Wsh * os.nch * os.Mrec > IA_XO_MAXREC)
+        return fail(IA_EINVAL, "ia_synthesize_level: exchange = 2: shard too large for the pruned scan's chunks");
+      XOScan xs{};
+      for (int p = 0; p < Wsh; p++) xs.area[p] = P.sharded ? xo_area(p, os.seq) : os.loc;
+      xs.flag = reinterpret_cast<const unsigned *>(os.loc + (os.ink ? XOLayout::QSEQ : XOLayout::FLAG));
+      xs.inv = c->xo_inv.as<int>();
+      xs.on = 1;
+      xs.s = P.sharded ? c->rank : (int)i;
+      xs.bpj = os.ink ? 1 : P.xo_bpj;
+      xs.Mrec = os.Mrec;
+      xs.seq = os.seq;
+      xs.err = c->xerr.as<unsigned>();
+      xs.timeout_ticks = IA_WAIT_TICKS;
+      K3pLaunch k{};  // the queries come from this process's area, the records go to the owners'
+      k.db = shard_db(x);
+      k.NT = n;
+      k.qf = os.loc + XOLayout::FRAG;
+      k.qinfo = reinterpret_cast<const float4 *>(os.loc + XOLayout::INFO);
+      k.order = reinterpret_cast<const int *>(os.loc + XOLayout::ORD);
+      k.tbox = reinterpret_cast<const float4 *>(os.loc + XOLayout::TBOX);
+      k.boxes = mas[i].boxes;
+      k.pos2row = mas[i].pos2row;
+      k.tnorm = c->tnorm.as<float>() + x.t0;
+      k.qt = os.ink ? os.QTs : P.xo_QTx;
+      k.M = sd.M;
+      k.Mpad = os.ink ? os.Mpj : os.Mrec;
+      k.nwg = os.nch;
+      k.nqb = os.nqb;
+      k.qt_end = Wsh * os.QTs;
+      k.pairs = tally.pairs();
+      k.tiles = tally.tiles();
+      k.step = sd.t;
+      k.r0 = sd.r0;
+      k.xo = &xs;
+      k.stamp = stamps.k3();
+      k.rec_wt = c->rec_wt;
+      if (ia_launch_k3p(k, c->k3p_variant, !os.ink, c->st)) return fail(IA_EINVAL, "pruned scan: no kernel instance for k3p_variant");
+      tally.add((double)n * Wsh * os.QTs, (double)n * os.nqb, 0., true,
+                scan_fixed_bytes((double)n * os.nqb, os.Mrec, (double)os.Mrec * os.nch * 24), (double)n * P.tile_bytes);
+    }
+    tally.end_step();
+    return IA_OK;
+  }
+  int owner_merge(const StepDesc &sd, const OwnerStep &os, const QBufs &q) {
+    const int64_t t = sd.t;
+    const int Wsh = P.Wsh;
+    // the next step's layout (fused merge + gather: each owner publishes its next queries)
+    const bool fuse_next = fuses_next(t);
+    StepDesc sn{};
+    int Mpj_n = 0;
+    bool ink_n = false;
+    if (fuse_next) {
+      int rc;
+      if ((rc = link.wait_dep(t + 1))) return rc;
+      sn.t = (int)(t + 1);
+      sn.J = 1;
+      ia_wavefront_step(g.bh, g.bw, t + 1, &sn.r0, &sn.M);
+      Mpj_n = (int)tile_pad(sn.M);
+      sn.Mpad = Mpj_n;
+      ink_n = Mpj_n <= ia_k3h_qtmax(g.KS) * IA_TILE && !c->xo_presort;
+    }
+    for (int jl = 0; jl < P.J; jl++) {
+      const size_t q0 = (size_t)jl * os.Mpj;
+      MergeArgs mx = ma;
+      mx.q64 = q.q64 + q0 * g.D;
+      mx.qn2 = q.qn2 + q0;
+      mx.qinfo = q.qinfo + 3 * q0;
+      mx.rec = reinterpret_cast<const float4 *>(os.loc + XOLayout::REC);
+      mx.xo_rts = reinterpret_cast<const unsigned long long *>(os.loc + XOLayout::RTS);
+      mx.nwg = Wsh * os.nch;
+      mx.rr = 1;
+      mx.NT = g.n_tiles;
+      mx.boxes = c->boxes.as<float4>();
+      mx.pos2row = g.pos2row;
+      mx.xo_inv = c->xo_inv.as<int>();
+      mx.xo_W = Wsh;
+      mx.xo_nch = os.nch;
+      mx.xo_Mrec = os.Mrec;
+      mx.xo_o0 = owner_of(jl);
+      mx.xo_M = sd.M;
+      mx.xo_QTs = os.QTs;
+      mx.xo_seq = os.seq;
+      mx.xo_err = c->xerr.as<unsigned>();
+      mx.xo_timeout = IA_WAIT_TICKS;
+      mx.stamp = stamps.mg();
+      if (!fuse_next) {
+        ia_launch_merge(g, os.s1, in.Aim, mx, c->win.as<Winner>(), in.job(jl), true, c->st);
+        continue;
+      }
+      NextStep nx = next_step(sn, jl, (size_t)jl * Mpj_n);
+      if (ink_n) {  // the next step's queries go straight to every rank's area (else its K2s sorts them)
+        nx.xp.W = P.sharded ? Wsh : 1;
+        for (int p = 0; p < nx.xp.W; p++) nx.xp.area[p] = xo_area(p, os.seq + 1);
+        nx.xp.slot0 = owner_of(jl) * Mpj_n;
+        nx.xp.seq = os.seq + 1;
+        if (P.sharded && c->xo_wait && jl == P.J - 1) {  // ranks: wait here for every owner's next queries
+          nx.wait_seq = reinterpret_cast<const unsigned *>(xo_area(c->rank, os.seq + 1) + XOLayout::QSEQ);
+          nx.wait_n = Wsh * Mpj_n;
+        }
+      }
+      ia_launch_merge_gather(g, os.s1, in.Aim, mx, in.job(jl), in.Bim, nx, true, c->st);
+    }
+    if (fuse_next) gathered = t + 1;
+    return IA_OK;
+  }
+};
+
+// ---- phase 5: results -----------------------------------------------------------------------
+// the stats words' reduction, the D2H copies of host-memory jobs, the level's one sync, and the
+// error words of the handoffs and exchanges
+static int finish_level(ia_ctx *c, const ia_level_args *args, const LevelPlan &P, const LevelInputs &in, bool chain,
+                        bool want_stats) {
+  const int64_t NB = P.NB;
+  if (want_stats)
+    for (int j = 0; j < P.J; j++) ia_launch_reduce_stats(in.jp[j].pstat, NB, c->counters.as<unsigned long long>(), c->st);
+  for (int j = 0; j < P.J; j++) {
     const ia_level_args *x = &args[j];
+    const JobPtrs &p = in.jp[j];
     if (x->mem != IA_MEM_HOST) continue;
-    HIP_TRY(hipMemcpyAsync(x->Bp, jp[j].Bp, nB * 8, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipMemcpyAsync(x->s_out, jp[j].s, (size_t)NB * 8, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipMemcpyAsync(x->im_out, jp[j].im, (size_t)NB * 4, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipMemcpyAsync(x->Bp, p.Bp, P.nB * 8, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipMemcpyAsync(x->s_out, p.s, (size_t)NB * 8, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipMemcpyAsync(x->im_out, p.im, (size_t)NB * 4, hipMemcpyDeviceToHost, c->st));
     if (x->dbg_src) {
-      HIP_TRY(hipMemcpyAsync(x->dbg_src, jp[j].dbg_src, (size_t)NB * 24, hipMemcpyDeviceToHost, c->st));
-      HIP_TRY(hipMemcpyAsync(x->dbg_dist, jp[j].dbg_dist, (size_t)NB * 16, hipMemcpyDeviceToHost, c->st));
+      HIP_TRY(hipMemcpyAsync(x->dbg_src, p.dbg_src, (size_t)NB * 24, hipMemcpyDeviceToHost, c->st));
+      HIP_TRY(hipMemcpyAsync(x->dbg_dist, p.dbg_dist, (size_t)NB * 16, hipMemcpyDeviceToHost, c->st));
     }
   }
   HIP_TRY(hipStreamSynchronize(c->st));
 #if IA_PROBE & 16
-  if (prune) ia_k3p_probe_dump();
+  if (P.prune) ia_k3p_probe_dump();
 #endif
   if (chain) {
     unsigned xe = 0;
     HIP_TRY(hipMemcpy(&xe, c->xerr.p, 4, hipMemcpyDeviceToHost));
     if (xe & 16) return fail(IA_EHIP, "ia_synthesize_level: a fused gather's handoff did not arrive within 20 s");
   }
-  if (xchg || xo) {
+  if (P.xchg || P.xo) {
     unsigned xe = 0;
     HIP_TRY(hipMemcpy(&xe, c->xerr.p, 4, hipMemcpyDeviceToHost));
     if (xe)
@@ -1716,189 +1866,248 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
                                 (xe & 4 ? "sorted queries" : xe & 8 ? "scan records" : "shard winner") +
                                 " did not arrive within 20 s (peer-write exchange)");
   }
-  if (stats) {
-    unsigned long long ctr[5], prs[4], pfull = 0, ptp = 0, ext[2] = {0, 0};
-    HIP_TRY(hipMemcpy(ctr, c->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));
-    {  // per-workgroup counter slots (no same-address atomics in the distance kernel)
-      std::vector<unsigned long long> slots(6 * IA_NWG_H);
-      HIP_TRY(hipMemcpy(slots.data(), c->pairs.p, slots.size() * 8, hipMemcpyDeviceToHost));
-      for (int j = 0; j < 4; j++) {
-        prs[j] = 0;
-        for (int w = 0; w < IA_NWG_H; w++) {
-          const unsigned long long v = slots[j * IA_NWG_H + w];
-          if (j < 2) {  // pair slots: (pairs with corrections << 32) + pairs (k3p_variant 14/15)
-            prs[j] += v & 0xffffffffull;
-            pfull += v >> 32;
-          } else {  // tile slots: (tiles with a filter-passing block << 32) + tiles loaded
-            prs[j] += v & 0xffffffffull;
-            ptp += v >> 32;
-          }
-        }
+  return IA_OK;
+}
+
+// option "stamps": the level's per-launch device times (K3p launches, then merges) and the
+// pruned scan's algorithmic bytes; db_stream = the DB bytes its kernels counted
+static int accumulate_stamp_stats(ia_ctx *c, const StampSlots &s, const ScanTally &tally, double db_stream, ia_stats *stats) {
+  const int64_t k3_n = s.k3_n, mg_n = s.mg_n;
+  if (const char *dp = std::getenv("IA_STAMP_DUMP")) {
+    // diagnostic: the raw per-workgroup stamps of this level's launches (K3p: IA_NWG_H slots
+    // per launch, merges: mg_stride slots; (start | 1, end) ticks of 100 MHz) appended to a file
+    std::vector<unsigned long long> r3((size_t)k3_n * IA_NWG_H * 2), rm((size_t)mg_n * s.mg_stride * 2);
+    HIP_TRY(hipMemcpy(r3.data(), c->stamp_k3.p, r3.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rm.data(), c->stamp_mg.p, rm.size() * 8, hipMemcpyDeviceToHost));
+    if (FILE *f = std::fopen(dp, "ab")) {
+      const int64_t hdr[4] = {k3_n, IA_NWG_H, mg_n, s.mg_stride};
+      std::fwrite(hdr, 8, 4, f);
+      std::fwrite(r3.data(), 8, r3.size(), f);
+      std::fwrite(rm.data(), 8, rm.size(), f);
+      std::fclose(f);
+    }
+  }
+  std::vector<unsigned long long> sp((size_t)2 * (k3_n + mg_n));  // (start, end) per launch: K3p, then merges
+  HIP_TRY(hipMemcpy(sp.data(), c->stamp_dur.p, sp.size() * 8, hipMemcpyDeviceToHost));
+  double tk = 0., tm = 0.;
+  for (int64_t i = 0; i < k3_n; i++) tk += (double)(sp[2 * i + 1] - sp[2 * i]);
+  for (int64_t i = k3_n; i < k3_n + mg_n; i++) tm += (double)(sp[2 * i + 1] - sp[2 * i]);
+  stats->k3p_stamp_ms += tk * 1e-5;  // 100 MHz ticks
+  {  // the launches' start spread and mean workgroup duration (k_stamp_durations span2)
+    std::vector<unsigned long long> s2((size_t)2 * k3_n);
+    HIP_TRY(hipMemcpy(s2.data(), c->stamp_dur.as<unsigned long long>() + 2 * (k3_n + mg_n), s2.size() * 8,
+                      hipMemcpyDeviceToHost));
+    double ss = 0., sw = 0.;
+    for (int64_t i = 0; i < k3_n; i++) {
+      ss += (double)s2[2 * i];
+      sw += (double)s2[2 * i + 1];
+    }
+    stats->k3p_stamp_start_ms += ss * 1e-5;
+    stats->k3p_stamp_wg_ms += sw * 1e-5;
+  }
+  stats->k3p_stamp_launches += k3_n;
+  stats->merge_stamp_ms += tm * 1e-5;
+  stats->merge_stamp_launches += mg_n;
+  // one scan and one merge per step (a one-job unsharded level): the idle time of the level's
+  // chain between its kernels, scan(t) -> merge(t) and merge(t) -> scan(t + 1)
+  if (k3_n == mg_n + 1 || k3_n == mg_n) {
+    const unsigned long long *m = sp.data() + 2 * k3_n;
+    double gap = 0., gsm = 0.;
+    int64_t ng = 0, nsm = 0;
+    for (int64_t i = 0; i < mg_n; i++) {
+      if (m[2 * i] && sp[2 * i + 1] && m[2 * i] >= sp[2 * i + 1]) {
+        gsm += (double)(m[2 * i] - sp[2 * i + 1]);
+        nsm++;
       }
-      for (int w = 0; w < IA_NWG_H; w++) {  // DB half-tiles loaded besides one per loaded tile
-        ext[0] += slots[4 * IA_NWG_H + w];
-        ext[1] += slots[5 * IA_NWG_H + w];
+      if (i + 1 < k3_n && sp[2 * (i + 1)] && m[2 * i + 1] && sp[2 * (i + 1)] >= m[2 * i + 1]) {
+        gap += (double)(sp[2 * (i + 1)] - m[2 * i + 1]);
+        ng++;
       }
     }
-    const double pair_flops = 2.0 * g.D * IA_TILE * IA_TILE;  // one (DB tile, query tile) pair
-    // algorithmic DB bytes of the pruned scan, as each launch's kernel counted them (ADVICE r4:
-    // steps wider than 512 queries run another variant than the option names): one half tile
-    // (hi or lo) per loaded tile + the extra halves (whole tiles: the lo halves; hi-only stream:
-    // the lo halves of the filter-passing tiles; two passes: the passing tiles again, whole)
-    auto tile_stream_bytes = [&](double tiles, double extra) { return 0.5 * ia_k3h_tile_bytes(g.KS) * (tiles + extra); };
-    if (prune) {
-      dist_flops = pair_flops * (double)(prs[0] + prs[1]);
-      flops_timed = pair_flops * (double)prs[1];
+    stats->stamp_gap_ms += (gap + gsm) * 1e-5;
+    stats->stamp_gaps += ng + nsm;
+    stats->stamp_gap_sm_ms += gsm * 1e-5;
+    stats->stamp_gaps_sm += nsm;
+    stats->stamp_window_ms += (double)(std::max(sp[2 * k3_n - 1], m[2 * mg_n - 1]) - sp[0]) * 1e-5;
+  }
+  stats->k3p_bytes_all += db_stream + tally.bytes_all_fixed;
+  // unique DB bytes: a launch reads each tile of its range at most once as
+  // far as the roofline is concerned, however many query blocks stream it
+  stats->k3p_bytes_unique_all += std::min(db_stream, tally.db_cap_all) + tally.bytes_all_fixed;
+  return IA_OK;
+}
+
+static int accumulate_stats(ia_ctx *c, const LevelPlan &P, const LevelRun &run, ia_stats *stats) {
+  const LevelGeo &g = P.g;
+  const ScanTally &tally = run.tally;
+  const bool prune = P.prune;
+  const int J = P.J;
+  unsigned long long ctr[5], prs[4], pfull = 0, ptp = 0, ext[2] = {0, 0};
+  HIP_TRY(hipMemcpy(ctr, c->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));
+  {  // per-workgroup counter slots (no same-address atomics in the distance kernel)
+    std::vector<unsigned long long> slots(6 * IA_NWG_H);
+    HIP_TRY(hipMemcpy(slots.data(), c->pairs.p, slots.size() * 8, hipMemcpyDeviceToHost));
+    for (int j = 0; j < 4; j++) {
+      prs[j] = 0;
+      for (int w = 0; w < IA_NWG_H; w++) {
+        const unsigned long long v = slots[j * IA_NWG_H + w];
+        // pair slots: (pairs with corrections << 32) + pairs; tile slots: (tiles with a
+        // filter-passing block << 32) + tiles loaded
+        prs[j] += v & 0xffffffffull;
+        (j < 2 ? pfull : ptp) += v >> 32;
+      }
     }
-    stats->pruned_levels += prune ? J : 0;
-    stats->dist_pairs += prune ? (double)(prs[0] + prs[1]) : pairs_full;
-    stats->dist_pairs_full += pairs_full;
-    stats->dist_tiles += prune ? (double)(prs[2] + prs[3]) : tiles_full;
-    stats->dist_tiles_full += tiles_full;
-    stats->dist_pairs_corrected += (double)pfull;
-    stats->dist_tiles_rows += (double)ptp;
-    float ms_db = 0.f, ms_syn = 0.f, ms_k1b = 0.f, ms_k1 = 0.f;
-    hipEventElapsedTime(&ms_db, c->lv0, c->lv1);
-    hipEventElapsedTime(&ms_syn, c->lv1, c->lv2);
-    hipEventElapsedTime(&ms_k1b, c->kb[0], c->kb[1]);
-    hipEventElapsedTime(&ms_k1, c->kb[2], c->kb[3]);
-    if (g.NA >= stats->build_rows) {  // K1b: A-side images read once, every fp64 row written; K1: this
-                                      // process's rows read, tiles written (the largest level seen)
-      if (g.NA > stats->build_rows) {
-        stats->k1b_ms = stats->k1b_bytes = stats->k1_ms = stats->k1_bytes = 0.;
-        stats->build_levels = 0;
-        stats->build_rows = g.NA;
-      }
-      const int DSb = ia_db64_stride(g.ch);
-      stats->k1b_ms += ms_k1b;
-      stats->k1b_bytes += (double)(nA + nAc) * (1 + g.n_ap) * 8 + (double)g.NA * DSb * 8;
-      if (ns > 0 && use_h) {
-        stats->k1_ms += ms_k1;
-        stats->k1_bytes += (double)std::min<int64_t>((int64_t)ns * IA_TILE, g.NA) * DSb * 8 + (double)ns * tile_bytes;
-      }
-      stats->build_levels += 1;
+    for (int w = 0; w < IA_NWG_H; w++) {  // DB half-tiles loaded besides one per loaded tile
+      ext[0] += slots[4 * IA_NWG_H + w];
+      ext[1] += slots[5 * IA_NWG_H + w];
     }
-    for (int64_t i = 0; i < n_gm; i++) {
-      float mg = 0.f, mm = 0.f;
-      hipEventElapsedTime(&mg, c->evg[2 * i], c->evg[2 * i + 1]);
-      hipEventElapsedTime(&mm, c->evm[2 * i], c->evm[2 * i + 1]);
-      stats->gather_ms_timed += mg;
-      stats->merge_ms_timed += mm;
+  }
+  const double pair_flops = 2.0 * g.D * IA_TILE * IA_TILE;  // one (DB tile, query tile) pair
+  // algorithmic DB bytes of the pruned scan, as each launch's kernel counted them (a
+  // step may run another kernel than the option names, ia_kernels.hip k3p_kernel): one half tile
+  // (hi or lo) per loaded tile + the extra halves (whole tiles: the lo halves; hi-only stream:
+  // the lo halves of the filter-passing tiles; two passes: the passing tiles again, whole)
+  auto tile_stream_bytes = [&](double tiles, double extra) { return 0.5 * ia_k3h_tile_bytes(g.KS) * (tiles + extra); };
+  const double dist_flops = prune ? pair_flops * (double)(prs[0] + prs[1]) : tally.dist_flops;
+  const double flops_timed = prune ? pair_flops * (double)prs[1] : tally.flops_timed;
+  stats->pruned_levels += prune ? J : 0;
+  stats->dist_pairs += prune ? (double)(prs[0] + prs[1]) : tally.pairs_full;
+  stats->dist_pairs_full += tally.pairs_full;
+  stats->dist_tiles += prune ? (double)(prs[2] + prs[3]) : tally.tiles_full;
+  stats->dist_tiles_full += tally.tiles_full;
+  stats->dist_pairs_corrected += (double)pfull;
+  stats->dist_tiles_rows += (double)ptp;
+  float ms_db = 0.f, ms_syn = 0.f, ms_k1b = 0.f, ms_k1 = 0.f;
+  hipEventElapsedTime(&ms_db, c->lv0, c->lv1);
+  hipEventElapsedTime(&ms_syn, c->lv1, c->lv2);
+  hipEventElapsedTime(&ms_k1b, c->kb[0], c->kb[1]);
+  hipEventElapsedTime(&ms_k1, c->kb[2], c->kb[3]);
+  if (g.NA >= stats->build_rows) {  // K1b: A-side images read once, every fp64 row written; K1: this
+                                    // process's rows read, tiles written (the largest level seen)
+    if (g.NA > stats->build_rows) {
+      stats->k1b_ms = stats->k1b_bytes = stats->k1_ms = stats->k1_bytes = 0.;
+      stats->build_levels = 0;
+      stats->build_rows = g.NA;
     }
-    stats->gather_launches_timed += n_gm;
-    stats->merge_launches_timed += n_gm;
-    stats->gather_bytes_timed += gather_bytes_timed;
-    stats->pixels += NB * J;
-    stats->steps += T;
-    stats->reranked += (int64_t)ctr[0];
-    stats->fallbacks += (int64_t)ctr[1];
-    stats->coherence_wins += (int64_t)ctr[2];
-    stats->bound_violations += (int64_t)ctr[3];
-    stats->kappa_ambiguous += (int64_t)ctr[4];
-    stats->f16_levels += use_h ? J : 0;
-    stats->db_ms += ms_db;
-    stats->synth_ms += ms_syn;
-    stats->dist_launches += dist_launches;
-    stats->dist_flops += dist_flops;
-    // the pruned scan's timing fields (prune_*, k3p_*, merge_stamp_*, stamp_*) describe the
-    // pruned levels with the largest DB seen (prune_rows: the bench's finest level), like k1*_ms
-    bool prune_acc = false;
-    if (prune && g.NA >= stats->prune_rows) {
-      if (g.NA > stats->prune_rows) {
-        stats->prune_ms_timed = stats->prune_flops_timed = stats->prune_bytes_timed = 0.;
-        stats->prune_launches_timed = 0;
-        stats->k3p_stamp_ms = stats->k3p_bytes_all = stats->merge_stamp_ms = stats->stamp_gap_ms = stats->stamp_window_ms = 0.;
-        stats->k3p_stamp_start_ms = stats->k3p_stamp_wg_ms = stats->stamp_gap_sm_ms = 0.;
-        stats->stamp_gaps_sm = 0;
-        stats->k3p_stamp_launches = stats->merge_stamp_launches = stats->stamp_gaps = 0;
-        stats->k3p_bytes_unique_all = 0.;
-        stats->prune_rows = g.NA;
-      }
-      prune_acc = true;
+    const int DSb = ia_db64_stride(g.ch);
+    stats->k1b_ms += ms_k1b;
+    stats->k1b_bytes += (double)(P.nA + P.nAc) * (1 + g.n_ap) * 8 + (double)g.NA * DSb * 8;
+    if (P.ns > 0 && P.use_h) {
+      stats->k1_ms += ms_k1;
+      stats->k1_bytes += (double)std::min<int64_t>((int64_t)P.ns * IA_TILE, g.NA) * DSb * 8 + (double)P.ns * P.tile_bytes;
     }
-    if (stamped && prune_acc && k3_n + mg_n > 0) {
-      if (const char *dp = std::getenv("IA_STAMP_DUMP")) {
-        // diagnostic: the raw per-workgroup stamps of this level's launches (K3p: IA_NWG_H slots
-        // per launch, merges: mg_stride slots; (start | 1, end) ticks of 100 MHz) appended to a file
-        std::vector<unsigned long long> r3((size_t)k3_n * IA_NWG_H * 2), rm((size_t)mg_n * mg_stride * 2);
-        HIP_TRY(hipMemcpy(r3.data(), c->stamp_k3.p, r3.size() * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(rm.data(), c->stamp_mg.p, rm.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = std::fopen(dp, "ab")) {
-          const int64_t hdr[4] = {k3_n, IA_NWG_H, mg_n, mg_stride};
-          std::fwrite(hdr, 8, 4, f);
-          std::fwrite(r3.data(), 8, r3.size(), f);
-          std::fwrite(rm.data(), 8, rm.size(), f);
-          std::fclose(f);
-        }
-      }
-      std::vector<unsigned long long> sp((size_t)2 * (k3_n + mg_n));  // (start, end) per launch: K3p, then merges
-      HIP_TRY(hipMemcpy(sp.data(), c->stamp_dur.p, sp.size() * 8, hipMemcpyDeviceToHost));
-      double tk = 0., tm = 0.;
-      for (int64_t i = 0; i < k3_n; i++) tk += (double)(sp[2 * i + 1] - sp[2 * i]);
-      for (int64_t i = k3_n; i < k3_n + mg_n; i++) tm += (double)(sp[2 * i + 1] - sp[2 * i]);
-      stats->k3p_stamp_ms += tk * 1e-5;  // 100 MHz ticks
-      {  // the launches' start spread and mean workgroup duration (k_stamp_durations span2)
-        std::vector<unsigned long long> s2((size_t)2 * k3_n);
-        HIP_TRY(hipMemcpy(s2.data(), c->stamp_dur.as<unsigned long long>() + 2 * (k3_n + mg_n), s2.size() * 8,
-                          hipMemcpyDeviceToHost));
-        double ss = 0., sw = 0.;
-        for (int64_t i = 0; i < k3_n; i++) {
-          ss += (double)s2[2 * i];
-          sw += (double)s2[2 * i + 1];
-        }
-        stats->k3p_stamp_start_ms += ss * 1e-5;
-        stats->k3p_stamp_wg_ms += sw * 1e-5;
-      }
-      stats->k3p_stamp_launches += k3_n;
-      stats->merge_stamp_ms += tm * 1e-5;
-      stats->merge_stamp_launches += mg_n;
-      // one scan and one merge per step (a one-job unsharded level): the idle time of the level's
-      // chain between its kernels, scan(t) -> merge(t) and merge(t) -> scan(t + 1)
-      if (k3_n == mg_n + 1 || k3_n == mg_n) {
-        const unsigned long long *m = sp.data() + 2 * k3_n;
-        double gap = 0., gsm = 0.;
-        int64_t ng = 0, nsm = 0;
-        for (int64_t i = 0; i < mg_n; i++) {
-          if (m[2 * i] && sp[2 * i + 1] && m[2 * i] >= sp[2 * i + 1]) {
-            gsm += (double)(m[2 * i] - sp[2 * i + 1]);
-            nsm++;
-          }
-          if (i + 1 < k3_n && sp[2 * (i + 1)] && m[2 * i + 1] && sp[2 * (i + 1)] >= m[2 * i + 1]) {
-            gap += (double)(sp[2 * (i + 1)] - m[2 * i + 1]);
-            ng++;
-          }
-        }
-        stats->stamp_gap_ms += (gap + gsm) * 1e-5;
-        stats->stamp_gaps += ng + nsm;
-        stats->stamp_gap_sm_ms += gsm * 1e-5;
-        stats->stamp_gaps_sm += nsm;
-        stats->stamp_window_ms += (double)(std::max(sp[2 * k3_n - 1], m[2 * mg_n - 1]) - sp[0]) * 1e-5;
-      }
-      const double db_stream = tile_stream_bytes((double)(prs[2] + prs[3]), (double)(ext[0] + ext[1]));
-      stats->k3p_bytes_all += db_stream + bytes_all_fixed;
-      // unique DB bytes: a launch reads each tile of its range at most once as
-      // far as the roofline is concerned, however many query blocks stream it
-      stats->k3p_bytes_unique_all += std::min(db_stream, db_cap_all) + bytes_all_fixed;
+    stats->build_levels += 1;
+  }
+  for (int64_t i = 0; i < run.n_gm; i++) {
+    float mg = 0.f, mm = 0.f;
+    hipEventElapsedTime(&mg, c->evg[2 * i], c->evg[2 * i + 1]);
+    hipEventElapsedTime(&mm, c->evm[2 * i], c->evm[2 * i + 1]);
+    stats->gather_ms_timed += mg;
+    stats->merge_ms_timed += mm;
+  }
+  stats->gather_launches_timed += run.n_gm;
+  stats->merge_launches_timed += run.n_gm;
+  stats->gather_bytes_timed += run.gather_bytes_timed;
+  stats->pixels += P.NB * J;
+  stats->steps += P.T;
+  stats->reranked += (int64_t)ctr[0];
+  stats->fallbacks += (int64_t)ctr[1];
+  stats->coherence_wins += (int64_t)ctr[2];
+  stats->bound_violations += (int64_t)ctr[3];
+  stats->kappa_ambiguous += (int64_t)ctr[4];
+  stats->f16_levels += P.use_h ? J : 0;
+  stats->db_ms += ms_db;
+  stats->synth_ms += ms_syn;
+  stats->dist_launches += tally.dist_launches;
+  stats->dist_flops += dist_flops;
+  // the pruned scan's timing fields (prune_*, k3p_*, merge_stamp_*, stamp_*) describe the
+  // pruned levels with the largest DB seen (prune_rows: the bench's finest level), like k1*_ms
+  bool prune_acc = false;
+  if (prune && g.NA >= stats->prune_rows) {
+    if (g.NA > stats->prune_rows) {
+      stats->prune_ms_timed = stats->prune_flops_timed = stats->prune_bytes_timed = 0.;
+      stats->prune_launches_timed = 0;
+      stats->k3p_stamp_ms = stats->k3p_bytes_all = stats->merge_stamp_ms = stats->stamp_gap_ms = stats->stamp_window_ms = 0.;
+      stats->k3p_stamp_start_ms = stats->k3p_stamp_wg_ms = stats->stamp_gap_sm_ms = 0.;
+      stats->stamp_gaps_sm = 0;
+      stats->k3p_stamp_launches = stats->merge_stamp_launches = stats->stamp_gaps = 0;
+      stats->k3p_bytes_unique_all = 0.;
+      stats->prune_rows = g.NA;
     }
-    if (stride && ns > 0) {
-      double tot = 0.;
-      for (int64_t i = 0; i < n_rec; i++) {
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, c->evs[2 * i], c->evs[2 * i + 1]);
-        tot += ms;
-      }
-      stats->dist_ms += tot;
-      stats->dist_launches_timed += launches_timed;
-      stats->dist_flops_timed += flops_timed;
-      if (prune_acc) {  // the pruned scan alone (bench roofline): time, MFMA flops, algorithmic bytes
-        stats->prune_ms_timed += tot;
-        stats->prune_launches_timed += launches_timed;
-        stats->prune_flops_timed += flops_timed;
-        stats->prune_bytes_timed += tile_stream_bytes((double)prs[3], (double)ext[1]) + bytes_timed_fixed;
-      }
+    prune_acc = true;
+  }
+  int rc;
+  if (run.stamps.on && prune_acc && run.stamps.k3_n + run.stamps.mg_n > 0 &&
+      (rc = accumulate_stamp_stats(c, run.stamps, tally, tile_stream_bytes((double)(prs[2] + prs[3]), (double)(ext[0] + ext[1])),
+                                   stats)))
+    return rc;
+  if (P.stride && P.ns > 0) {
+    double tot = 0.;
+    for (int64_t i = 0; i < tally.n_rec; i++) {
+      float ms = 0.f;
+      hipEventElapsedTime(&ms, c->evs[2 * i], c->evs[2 * i + 1]);
+      tot += ms;
+    }
+    stats->dist_ms += tot;
+    stats->dist_launches_timed += tally.launches_timed;
+    stats->dist_flops_timed += flops_timed;
+    if (prune_acc) {  // the pruned scan alone (bench roofline): time, MFMA flops, algorithmic bytes
+      stats->prune_ms_timed += tot;
+      stats->prune_launches_timed += tally.launches_timed;
+      stats->prune_flops_timed += flops_timed;
+      stats->prune_bytes_timed += tile_stream_bytes((double)prs[3], (double)ext[1]) + tally.bytes_timed_fixed;
     }
   }
   return IA_OK;
+}
+
+int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_stats *stats) {
+  if (!c || !args) return fail(IA_EINVAL, "ia_synthesize_level: NULL argument");
+  if (n_jobs < 1 || n_jobs > IA_MAX_JOBS)
+    return fail(IA_EINVAL, "ia_synthesize_levels: n_jobs must be 1.." + std::to_string(IA_MAX_JOBS));
+  const ia_level_args *a = &args[0];
+  int rc;
+  for (int j = 0; j < n_jobs; j++) {
+    const ia_level_args *x = &args[j];
+    if ((rc = check_level_args(x))) return rc;
+    if (x->ch != a->ch || x->n_ap != a->n_ap || x->a_h != a->a_h || x->a_w != a->a_w || x->b_h != a->b_h ||
+        x->b_w != a->b_w || x->mem != a->mem)
+      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch has the same shapes, channels and mem kind");
+    if (x->A != a->A || x->Ac != a->Ac || x->Ap != a->Ap || x->Apc != a->Apc)
+      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch shares the A side (same A / A' buffers)");
+  }
+  HIP_TRY(hipSetDevice(c->dev));
+
+  // plan and stage (the plan's second half needs the matcher: one device read-back)
+  LevelPlan P;
+  LevelInputs in;
+  bool use_h = false;
+  if ((rc = plan_shards(c, args, n_jobs, P)) || (rc = stage_level(c, args, P, in)) || (rc = probe_matcher(c, P, in, &use_h)) ||
+      (rc = plan_scan(c, use_h, P)) || (rc = stage_jobs(c, P, in)) || (rc = ensure_scratch(c, P)))
+    return rc;
+  // the guards fire on every return from here on and outlive the step loop: the dependents'
+  // waits released (PipelineLink), the chain reservation returned, the used stamp slots cleared
+  StampSlots stamps;
+  if ((rc = stamps.open(c, P))) return rc;
+  HIP_TRY(hipMemsetAsync(c->pairs.p, 0, 6 * IA_NWG_H * 8, c->st));  // the scans' per-workgroup counters (ScanTally)
+  HIP_TRY(hipMemsetAsync(c->Rbits.p, 0, 4, c->st));
+  HIP_TRY(hipMemsetAsync(c->counters.p, 0, 5 * 8, c->st));
+  double ufac = 0.;
+  if ((rc = build_level_db(c, P, in, &ufac))) return rc;
+
+  ChainReservation chain_res;
+  PipelineLink link;
+  LevelRun run(c, P, in, stamps, link, chain_res, ufac);
+  run.init_merge_args();
+  if ((rc = run.init_chain()) || (rc = link.open(c, P.T))) return rc;
+  for (int64_t t = 0; t < P.T; link.mark_step(t), t++)
+    if ((rc = link.wait_dep(t)) || (rc = run.step(t))) return rc;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->lv2, c->st));
+  stamps.durations();  // (the slots this level wrote are cleared when the call returns)
+
+  if ((rc = finish_level(c, args, P, in, run.chain, stats != nullptr))) return rc;
+  return stats ? accumulate_stats(c, P, run, stats) : IA_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1993,7 +2202,7 @@ int ia_k3_microbench(ia_ctx *c, int64_t n_rows, int M, int reps, double *us_per_
   ia_launch_fill_random_f16(c->qf.p, (int64_t)qt * IA_TILE * row_bytes / 2, 777u, c->st);
   auto launch = [&]() {
     ia_launch_k3h(KS, qt, c->db.p, c->qf.p, n_tiles, tpw, 0, M, nwg, 0, n_tiles, c->rec.as<float4>(), c->recT.as<float>(),
-                  c->k3_variant, c->st);
+                  c->st);
   };
   for (int i = 0; i < 3; i++) launch();
   HIP_TRY(hipEventRecord(c->lv0, c->st));

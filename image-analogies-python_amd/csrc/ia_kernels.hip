@@ -2919,14 +2919,6 @@ void ia_launch_coherence_batch(const double *pts, int64_t n, int d, const double
 double ia_k3h_tile_bytes(int KS) { return KS == 4 ? 16.0 * TileFmt<4>::STRIDE : KS == 7 ? 16.0 * TileFmt<7>::STRIDE : 0.; }
 int ia_ks_for(int ch) { return ch == 1 ? 4 : ch == 2 ? 7 : 0; }  // 3 channels: fp32 matcher
 int ia_k3h_qtmax(int KS) { return KS == 4 ? 11 : 8; }
-// waves per workgroup of the K3h instance selected by (KS, qt, variant) (ia_k3h.hip getters)
-static int k3h_waves(int KS, int qt, int variant) {
-  return IA_WGH / IA_WAVE;
-}
-static size_t k3h_lds(int KS, int qt, int nw) {
-  const size_t q = (size_t)qt * 2 * KS * IA_WAVE * 16, m = (size_t)nw * qt * IA_TILE * sizeof(Top2);
-  return q > m ? q : m;
-}
 size_t ia_k3h_lds(int KS, int qt) {
   const size_t q = (size_t)qt * 2 * KS * IA_WAVE * 16, m = (size_t)(IA_WGH / IA_WAVE) * qt * IA_TILE * sizeof(Top2);
   return q > m ? q : m;
@@ -3000,9 +2992,8 @@ static void launch_gather_p_t(const LevelGeo &g, const StepDesc &sd, const Imgs 
 }
 void ia_launch_gather_p(const LevelGeo &g, const StepDesc &sd, const Imgs &B, const JobSet &jobs, const double *mu,
                         double *q64, double *qn2, void *qf, const double *db64, const double *basis, double ufac,
-                        float4 *qinfo, const Imgs &A, int img_rows, hipStream_t st, const XOPub *xp) {
+                        float4 *qinfo, const Imgs &A, hipStream_t st, const XOPub *xp) {
   const XOPub x = xp ? *xp : XOPub{};
-  (void)img_rows;
   launch_gather_p_t<false>(g, sd, B, jobs, mu, q64, qn2, qf, db64, basis, ufac, qinfo, A, x, st);
 }
 
@@ -3013,22 +3004,20 @@ IA_K3H_DECL(4, 1) IA_K3H_DECL(4, 2) IA_K3H_DECL(4, 3) IA_K3H_DECL(4, 4) IA_K3H_D
 IA_K3H_DECL(4, 7) IA_K3H_DECL(4, 8) IA_K3H_DECL(4, 9) IA_K3H_DECL(4, 10) IA_K3H_DECL(4, 11)
 IA_K3H_DECL(7, 1) IA_K3H_DECL(7, 2) IA_K3H_DECL(7, 3) IA_K3H_DECL(7, 4) IA_K3H_DECL(7, 5) IA_K3H_DECL(7, 6)
 IA_K3H_DECL(7, 7) IA_K3H_DECL(7, 8)
-static k3h_fn k3h_get(int KS, int qt, int variant) {
+static k3h_fn k3h_get(int KS, int qt) {
   typedef k3h_fn (*getter)(int);
   static const getter g4[] = {ia_k3h_get_4_1, ia_k3h_get_4_2, ia_k3h_get_4_3, ia_k3h_get_4_4,  ia_k3h_get_4_5, ia_k3h_get_4_6,
                               ia_k3h_get_4_7, ia_k3h_get_4_8, ia_k3h_get_4_9, ia_k3h_get_4_10, ia_k3h_get_4_11};
   static const getter g7[] = {ia_k3h_get_7_1, ia_k3h_get_7_2, ia_k3h_get_7_3, ia_k3h_get_7_4,
                               ia_k3h_get_7_5, ia_k3h_get_7_6, ia_k3h_get_7_7, ia_k3h_get_7_8};
-  return KS == 4 ? g4[qt - 1](variant) : g7[qt - 1](variant);
+  return KS == 4 ? g4[qt - 1](1) : g7[qt - 1](1);  // the packed-index epilogue, the only one built
 }
 void ia_launch_k3h(int KS, int qt, const void *db, const void *qf, int n_tiles, int tpw, int qt0, int M, int nwg, int row0,
-                   int NT, float4 *rec, float *recT, int variant, hipStream_t st) {
-  const k3h_fn fn = k3h_get(KS, qt, variant);
-  const int nw = k3h_waves(KS, qt, variant);
-  const size_t lds = k3h_lds(KS, qt, nw);
+                   int NT, float4 *rec, float *recT, hipStream_t st) {
+  const k3h_fn fn = k3h_get(KS, qt);
   allow_full_lds((const void *)fn);
-  hipLaunchKernelGGL(fn, dim3(nwg), dim3(nw * IA_WAVE), lds, st, (const h16x8 *)db, (const h16x8 *)qf, n_tiles, tpw, qt0, M, nwg,
-                     row0, NT, rec, recT);
+  hipLaunchKernelGGL(fn, dim3(nwg), dim3(IA_WGH), ia_k3h_lds(KS, qt), st, (const h16x8 *)db, (const h16x8 *)qf, n_tiles, tpw,
+                     qt0, M, nwg, row0, NT, rec, recT);
 }
 
 // pruned split-f16 distance kernels (ia_k3h.hip k3h_prune, 1 channel)
@@ -3040,22 +3029,27 @@ size_t ia_k3p_lds(int qt, int Mpad) {
   const size_t qfrag = (size_t)qt * 8 * IA_WAVE * 16;  // KS = 4: NP = 8 h16x8 per lane
   return qfrag + NQ * 36 + (size_t)qt * 32 + (size_t)((qt + 3) & ~3) * 4 + (size_t)Mpad * 8;
 }
-int ia_launch_k3p(int qt, const void *db, const void *qf, const float4 *qinfo, const float4 *boxes, const int *pos2row,
-                   int NT, int qt0, int M, int Mpad, int nwg, float4 *rec, float *recT, unsigned long long *pairs,
-                   unsigned long long *tiles, int variant, int step, const int *ord_in, int n_in, int r0, int *ord_out,
-                   const float4 *tbox, const float *tnorm, hipStream_t st, int nqb, int qt_end, const XOScan *xo,
-                   unsigned long long *stamp, int rec_wt) {
+// The one place that decides which pruned-scan kernel a launch runs: from option "k3p_variant",
+// whether the queries arrive presorted and whether this is an owner-computes scan; then by what
+// fits.  fn = nullptr: the library holds no instance (ia_set_option accepts only built variants).
+struct K3pKernel {
+  k3p_fn fn;
+  size_t lds;  // dynamic LDS bytes
+};
+static K3pKernel k3p_kernel(int option, bool presorted, bool owner_scan, int qt, int Mpad, int kmax) {
   typedef k3p_fn (*getter)(int);
   static const getter g4[] = {ia_k3p_get_4_1, ia_k3p_get_4_2, ia_k3p_get_4_3, ia_k3p_get_4_4,  ia_k3p_get_4_5, ia_k3p_get_4_6,
                               ia_k3p_get_4_7, ia_k3p_get_4_8, ia_k3p_get_4_9, ia_k3p_get_4_10, ia_k3p_get_4_11};
-  const int kmax = (NT + nwg - 1) / nwg;  // DB tiles per workgroup
-  const int rev = step & 1;  // alternate steps walk in reverse
-  // the in-kernel sort (20, 22, 24) holds <= 512 queries (wider: the host ran K2s, the presorted
-  // form 21 / 25); every variant walks any number of tiles (the host keeps kmax <= IA_K3P_MAXK_LDS)
-  const bool in_kernel_sort = variant == 20 || variant == 22 || variant == 24;
-  if (in_kernel_sort && Mpad > 512) variant = 21;
+  // the option's in-kernel-sort form (20 / 22 / 24) or its presorted form: 21, or the two-pass
+  // 25 under 24 / 25 (round 6, on the trimmed stream: cfg4 6.66 -> 6.91 M px/s against 21's whole
+  // tiles) - owner-computes scans take 25 only where it was asked for by name
+  int variant;
+  if (presorted) variant = option == 25 || (option == 24 && !owner_scan) ? 25 : 21;
+  else variant = option == 21 ? 20 : option == 25 ? 24 : option;
+  // the in-kernel sort holds <= 512 queries (the callers sort wider steps first, K2s); every
+  // variant walks any number of tiles (the host keeps kmax <= IA_K3P_MAXK_LDS)
+  if (!presorted && Mpad > 512) variant = 21;
   const size_t NQ = (size_t)qt * IA_TILE;
-  const int nthr = IA_WGH;
   auto dyn_lds = [&](int v) {
     const bool pre = v == 21 || v == 25;
     const size_t qfrag = (size_t)qt * (v >= 24 ? 4 : 8) * IA_WAVE * 16;  // v24 / 25: hi pieces only
@@ -3063,36 +3057,39 @@ int ia_launch_k3p(int qt, const void *db, const void *qf, const float4 *qinfo, c
                    : ia_k3p_lds(qt, Mpad) - (size_t)qt * 8 * IA_WAVE * 16 + qfrag + (size_t)Mpad * 4 + (size_t)kmax * 40;
     l += NQ * 8 + (size_t)kmax * 4;            // (z, w) per sorted query slot, R_t per tile
     if (v >= 24) l += (size_t)kmax * 8;        // the filter-passing tiles and their blocks
-    size_t red = (size_t)(nthr / IA_WAVE) * qt * IA_TILE * 20;  // the subset merge's Top2 area
-    if (v >= 24) red = std::max(red, (size_t)(nthr / IA_WAVE) * qt * IA_WAVE * 12);  // (every lane's subset)
+    size_t red = (size_t)(IA_WGH / IA_WAVE) * qt * IA_TILE * 20;  // the subset merge's Top2 area
+    if (v >= 24) red = std::max(red, (size_t)(IA_WGH / IA_WAVE) * qt * IA_WAVE * 12);  // (every lane's subset)
     return l > red ? l : red;
   };
-  size_t lds = dyn_lds(variant);
   if (variant >= 24) {  // the static LDS-DMA rings (86 KiB) + this launch's dynamic part must fit 160 KiB
     hipFuncAttributes fa;
     const k3p_fn f24 = g4[qt - 1](variant);
     const size_t stat = f24 && hipFuncGetAttributes(&fa, (const void *)f24) == hipSuccess ? fa.sharedSizeBytes : 0;
     // (and the second pass stages the lo pieces + a row map of the WG's tiles in the rings' 84 KiB)
     const bool ring_fits = (size_t)qt * 4 * IA_WAVE * 16 + (size_t)kmax * IA_TILE * 4 <= (size_t)8 * 3 * 3584;
-    if (!f24 || !ring_fits || stat + lds > 160 * 1024) {  // (many tiles per workgroup or wide steps): the one-pass forms
-      variant = variant == 25 ? 21 : 22;
-      lds = dyn_lds(variant);
-    }
+    // (many tiles per workgroup or wide steps): the one-pass forms
+    if (!f24 || !ring_fits || stat + dyn_lds(variant) > 160 * 1024) variant = variant == 25 ? 21 : 22;
   }
-  const k3p_fn fn = g4[qt - 1](variant);
-  // (the host accepts only the built variants, ia_set_option; a missing instance is an error the
-  // level reports, never a silently skipped scan whose stale records the merge would consume)
-  if (!fn) return -1;  // IA_EINVAL (include/ia.h)
-  const bool pre = variant == 21 || variant == 25;
-  // nqb > 1 (presorted variants only): one launch of nqb query blocks x nwg DB chunks
-  if (!pre && !(xo && xo->on)) nqb = 1;
-  if (nqb == 1) qt_end = qt0 + qt;
+  return {g4[qt - 1](variant), dyn_lds(variant)};
+}
+int ia_launch_k3p(const K3pLaunch &a, int option, bool presorted, hipStream_t st) {
+  const bool owner_scan = a.xo && a.xo->on;
+  const K3pKernel k = k3p_kernel(option, presorted, owner_scan, a.qt, a.Mpad, (a.NT + a.nwg - 1) / a.nwg);
+  // (a missing instance is an error the level reports, never a silently skipped scan whose stale
+  // records the merge would consume)
+  if (!k.fn) return -1;  // IA_EINVAL (include/ia.h)
+  // nqb > 1 (presorted kernels and owner-computes scans only): one launch of nqb query blocks x
+  // nwg DB chunks
+  const int nqb = presorted || owner_scan ? a.nqb : 1;
+  const int qt_end = nqb == 1 ? a.qt0 + a.qt : a.qt_end;
   XOScan x{};  // off unless an owner-computes step passes its exchange
-  if (xo) x = *xo;
-  x.stamp = stamp;
-  x.rec_wt = rec_wt;
-  allow_full_lds((const void *)fn);
-  hipLaunchKernelGGL(fn, dim3(nqb * nwg), dim3(nthr), lds, st, (const h16x8 *)db, (const h16x8 *)qf, qinfo, boxes, pos2row,
-                     NT, qt0, M, Mpad, nwg, rec, recT, pairs, tiles, rev, ord_in, n_in, r0, ord_out, tbox, tnorm, nqb, qt_end, x);
+  if (a.xo) x = *a.xo;
+  x.stamp = a.stamp;
+  x.rec_wt = a.rec_wt;
+  allow_full_lds((const void *)k.fn);
+  // (alternate steps walk in reverse; the kernel's n_in / ord_out arguments are unused)
+  hipLaunchKernelGGL(k.fn, dim3(nqb * a.nwg), dim3(IA_WGH), k.lds, st, (const h16x8 *)a.db, (const h16x8 *)a.qf, a.qinfo, a.boxes,
+                     a.pos2row, a.NT, a.qt0, a.M, a.Mpad, a.nwg, a.rec, a.recT, a.pairs, a.tiles, a.step & 1, a.order, 0, a.r0,
+                     nullptr, a.tbox, a.tnorm, nqb, qt_end, x);
   return 0;
 }

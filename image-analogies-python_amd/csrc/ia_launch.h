@@ -45,7 +45,7 @@ void ia_launch_db_build_h(const LevelGeo &g, const Imgs &A, const double *db64, 
 void ia_launch_gather_h(const LevelGeo &g, const StepDesc &sd, const Imgs &B, const JobSet &jobs, const double *mu,
                         double *q64, double *qn2, void *qf, hipStream_t st);
 void ia_launch_k3h(int KS, int qt, const void *db, const void *qf, int n_tiles, int tpw, int qt0, int M, int nwg, int row0,
-                   int NT, float4 *rec, float *recT, int variant, hipStream_t st);
+                   int NT, float4 *rec, float *recT, hipStream_t st);
 void ia_launch_fill_random_f16(void *p, int64_t n, unsigned seed, hipStream_t st);
 // certified pruned scan: per-level setup (ia_prune.hip)
 void ia_launch_cov(const double *db64, int64_t NA, int64_t stride, int nwg, const double *mu_part, double *part,
@@ -59,19 +59,40 @@ void ia_launch_table_boxes(const int *sorted_rows, const double *proj, int64_t N
                            float *boxes, const float *rnorm, float *tnorm, hipStream_t st);
 void ia_launch_gather_p(const LevelGeo &g, const StepDesc &sd, const Imgs &B, const JobSet &jobs, const double *mu,
                         double *q64, double *qn2, void *qf, const double *db64, const double *basis, double ufac,
-                        float4 *qinfo, const Imgs &A, int img_rows, hipStream_t st, const XOPub *xp = nullptr);
+                        float4 *qinfo, const Imgs &A, hipStream_t st, const XOPub *xp = nullptr);
 void ia_launch_query_sort(const float4 *qinfo, const void *qf, int Mpad, int KS, int *order, float4 *sq, void *qfs,
                           float4 *tbox, hipStream_t st);
 // owner-computes sharded step (exchange = 2): the owner's queries sorted into every rank's area
 void ia_launch_query_sort_xo(const float4 *qinfo, const void *qf, const XOSort &xs, hipStream_t st);
 size_t ia_k3p_lds(int qt, int Mpad);
 void ia_merge_gather_occupancy(int *vgprs, int *blocks_per_cu, int *wg_threads);
+// One pruned scan launch (ia_k3h.hip k3h_prune3).  The caller names option "k3p_variant" and
+// says whether the queries arrive presorted (K2s or the previous fused launch's gathers sorted
+// them: qf / qinfo / order / tbox are then k_query_sort's outputs); which kernel instance that
+// means for this launch is decided next to the launcher (ia_kernels.hip k3p_kernel).
+struct K3pLaunch {
+  const void *db;              // the scanned DB slice: its first stored tile ...
+  int NT;                      // ... and its tiles
+  const void *qf;              // the step's query fragments ...
+  const float4 *qinfo;         // ... and pruning records
+  const int *order = nullptr;  // presorted: sorted slot -> query ...
+  const float4 *tbox = nullptr;  // ... and the sorted query tiles' boxes (nullptr: taken from the slice)
+  const float4 *boxes;         // of the slice: tile boxes, position -> row, R_t per tile
+  const int *pos2row;
+  const float *tnorm;
+  int qt, qt0, M, Mpad;        // query tiles per block, first tile, the step's queries (padded)
+  int nwg;                     // DB chunks: workgroups per query block
+  int nqb = 1, qt_end = 0;     // presorted / owner-computes: query blocks of one launch, their last tile
+  float4 *rec = nullptr;       // records (owner-computes: pushed to the owners' areas instead)
+  float *recT = nullptr;
+  unsigned long long *pairs, *tiles;  // per-workgroup counter slots
+  int step, r0;                // step parity picks the walk direction
+  const XOScan *xo = nullptr;  // owner-computes step: its exchange
+  unsigned long long *stamp = nullptr;  // option "stamps"
+  int rec_wt = 0;              // option "rec_wt"
+};
 // returns IA_EINVAL (nothing launched) when no kernel instance exists for the variant
-int ia_launch_k3p(int qt, const void *db, const void *qf, const float4 *qinfo, const float4 *boxes, const int *pos2row,
-                   int NT, int qt0, int M, int Mpad, int nwg, float4 *rec, float *recT, unsigned long long *pairs,
-                   unsigned long long *tiles, int variant, int step, const int *ord_in, int n_in, int r0, int *ord_out,
-                   const float4 *tbox, const float *tnorm, hipStream_t st, int nqb = 1, int qt_end = 0,
-                   const XOScan *xo = nullptr, unsigned long long *stamp = nullptr, int rec_wt = 0);
+int ia_launch_k3p(const K3pLaunch &a, int option, bool presorted, hipStream_t st);
 // GPU preprocessing (ia_pyramid.hip)
 void ia_launch_pyramid_reduce(const double *in, double *out, double *tmp, double *sm, double *mm, int h, int w, int ch,
                               const double *w7, hipStream_t st);

@@ -68,6 +68,34 @@ def check_debug_records(z, out, Bp, st, name=''):
 # library defaults of include/ia.h (ia_set_option has no getter: tests restore these by name)
 PRUNE_MIN_ROWS_DEFAULT = 1 << 19
 
+
+def scan_counts(z, J, qtmax=11):
+    """What the scan launch counters of one run over every level of fixture z with J batched jobs
+    must add up to, per level: n = DB tiles of 32 rows, steps = the wavefront steps that hold a
+    query, qtt / nqb = their query tiles and query blocks (qtmax tiles per block: 11 is the
+    1-channel split-f16 scan's, ia_k3h_qtmax) summed over those steps.  Every scan path visits each
+    (DB tile, query tile) pair and each (DB tile, query block) once per step, so
+    dist_pairs_full = sum n qtt and dist_tiles_full = sum n nqb whatever kernel runs; only the
+    launch count tells the paths apart (one per block, or one per step and shard)."""
+    from ia_amd import _native
+    out = []
+    for level in range(1, z['L']):
+        a_h, a_w = z['A_pyr'][level].shape[:2]
+        h, w = z['B_pyr'][level].shape[:2]
+        assert z['A_pyr'][level].ndim == 2 or z['A_pyr'][level].shape[2] == 1   # qtmax = 11
+        T, _ = _native.wavefront_shape(h, w)
+        M = [m for m in (_native.wavefront_step(h, w, t)[1] for t in range(T)) if m > 0]
+        qtt = [-(-J * m // 32) for m in M]
+        out.append(dict(n=-(-len(z['Ap_pyr']) * a_h * a_w // 32), steps=len(M), qtt=sum(qtt),
+                        nqb=sum(-(-q // qtmax) for q in qtt)))
+    return out
+
+
+def sharded_scan_launches(z, J, W):
+    """dist_launches of a run whose steps each take one scan launch per shard: W on the levels
+    that shard (>= 64 DB tiles per shard), 1 on those that replicate."""
+    return sum(c['steps'] * (W if c['n'] >= 64 * W else 1) for c in scan_counts(z, J))
+
 # round 6: reference run at BASELINE config 2's shape (512^2, the finest 5 levels), the size at
 # which the product's default path prunes; 'slim' fixture (oracle/gen_golden.py run_case slim=True)
 SLIM_CASES = [c for c in ['g512', 'g64slim'] if os.path.exists(os.path.join(GOLDEN, 'e2e_%s.npz' % c))]

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch  # noqa: F401  (before libia loads: torch's HIP runtime must be the process's first)
 
-from golden_util import load_e2e
+from golden_util import load_e2e, scan_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -200,10 +200,17 @@ def test_batched_g256_wide_steps_match_reference(ctx, mode):
         assert stb.pruned_levels == 8 * (z['L'] - 1)
     # two query blocks on the 256^2 level: more scan launches than steps, except in the pruned
     # scan's one-launch form (one launch per step, twice the box-needed tile visits)
+    # every path visits each (DB tile, query tile) and (DB tile, query block) once per step; the
+    # launch count names the path (the scans are all exact, so only it shows a step routed elsewhere)
+    cnt = scan_counts(z, 8)
+    print(mode, stb.dist_pairs_full, stb.dist_tiles_full, stb.dist_launches, stb.steps, cnt)
+    assert stb.dist_pairs_full == sum(c['n'] * c['qtt'] for c in cnt)
+    assert stb.dist_tiles_full == sum(c['n'] * c['nqb'] for c in cnt)
     if mode in ('unpruned', 'pruned_seq'):
+        assert stb.dist_launches == sum(c['nqb'] for c in cnt)
         assert stb.dist_launches > stb.steps
     else:
-        assert stb.dist_launches <= stb.steps
+        assert stb.dist_launches == sum(c['steps'] for c in cnt)   # (<= steps: some hold no query)
 
 
 def test_cfg5_sweep_full_size(ctx):

@@ -311,7 +311,7 @@ def test_stamps_change_nothing(octx, name, setting):
 
 @pytest.mark.skipif(not _have(['g256']), reason='fixture g256 absent')
 def test_stamp_slots_are_clean_for_the_next_run(octx):
-    """The slots a level wrote are cleared when its call returns (StampClear): after the stamped
+    """The slots a level wrote are cleared when its call returns (StampSlots): after the stamped
     g256 (256 scan workgroups per launch) the stamped g64 (128 at most) on the same context must
     report its own launches only.  A stale slot shows up as a launch that "started" during the
     earlier run: a window reaching back over that run and the host time in between."""

@@ -12,7 +12,7 @@ peers' buffers aliased to this process's own."""
 import numpy as np
 import pytest
 
-from golden_util import BIG_CASES, load_e2e
+from golden_util import BIG_CASES, load_e2e, sharded_scan_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -106,8 +106,11 @@ def test_unpruned_levels_replicate_by_default(ctx):
     _, _, st0 = _run(ctx, z, 2, False, 1, shard_unpruned=0)
     _, _, st1 = _run(ctx, z, 2, False, 1, shard_unpruned=1)
     _, _, st2 = _run(ctx, z, 2, True, 1, shard_unpruned=0)
-    assert st0.dist_launches <= st0.steps          # one scan per (non-empty) step
-    assert st1.dist_launches > st0.dist_launches and st2.dist_launches > st0.dist_launches
+    print(st0.dist_launches, st1.dist_launches, st2.dist_launches, st0.steps)
+    assert st0.dist_launches == sharded_scan_launches(z, 1, 1)   # one scan per step that holds a query
+    assert st1.dist_launches == sharded_scan_launches(z, 1, 2)   # W on the levels of >= 64 W DB tiles
+    assert st2.dist_launches == sharded_scan_launches(z, 1, 2)
+    assert st1.dist_launches > st0.dist_launches
 
 
 def _run_batch(ctx, z, jobs, W, exchange, prune_all=True):
@@ -164,6 +167,9 @@ def test_emulated_shards_batched_jobs_match_reference(ctx, W, exchange):
             assert np.array_equal(S[j][level], Su[j][level]) and np.array_equal(IM[j][level], IMu[j][level]), (j, level)
             assert np.array_equal(jb[j][1][level], ju[j][1][level]), (j, level)
     assert st.bound_violations == 0 and st.kappa_ambiguous == 0 and st.pixels == stu.pixels
+    # one scan per shard and step (two query blocks: one launch, on every exchange path)
+    print(W, exchange, st.dist_launches, stu.dist_launches)
+    assert st.dist_launches == sharded_scan_launches(z, len(jb), W)
     assert st.dist_launches > stu.dist_launches   # W shard scans per sharded step
 
 
