@@ -135,7 +135,7 @@ struct ia_ctx {
   int prune_group = 1;           // option "prune_group": Morton tiles interleaved in groups of G (ia_prune.hip k_make_table)
   int matcher = IA_MATCH_F16X3;  // option "matcher"
   int k3p_variant = 24;          // option "k3p_variant": pruned-scan kernel version (ia_k3h.hip k3h_prune*)
-  int k3_variant = 1;            // option "k3_variant": K3h epilogue (0 compare/select, 1 packed index)
+  int k3_variant = 1;            // option "k3_variant": K3h epilogue (1 = packed index, the only one built)
   int k3p_blocks = 1;            // option "k3p_blocks": 1 = a wide step's presorted pruned scan is one launch over
                                  // all its query blocks (2-D grid); 0 = one launch per block
   int fuse_gather = 1;           // option "fuse_gather": 1 = K4 of step t and K2p of step t + 1 in one launch
@@ -1964,7 +1964,7 @@ static int accumulate_stats(ia_ctx *c, const LevelPlan &P, const LevelRun &run, 
   }
   const double pair_flops = 2.0 * g.D * IA_TILE * IA_TILE;  // one (DB tile, query tile) pair
   // algorithmic DB bytes of the pruned scan, as each launch's kernel counted them (a
-  // step may run another kernel than the option names, ia_kernels.hip k3p_kernel): one half tile
+  // step may run another kernel than the option names, ia_k3p_launch.hip k3p_kernel): one half tile
   // (hi or lo) per loaded tile + the extra halves (whole tiles: the lo halves; hi-only stream:
   // the lo halves of the filter-passing tiles; two passes: the passing tiles again, whole)
   auto tile_stream_bytes = [&](double tiles, double extra) { return 0.5 * ia_k3h_tile_bytes(g.KS) * (tiles + extra); };

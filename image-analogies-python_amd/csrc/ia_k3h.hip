@@ -13,6 +13,7 @@
 #include "ia_internal.h"
 #include "ia_top2.h"
 #include "ia_prune.h"
+#include "ia_k3p_lds.h"
 
 template <int KS>
 __device__ __forceinline__ void ld_tile(h16x8 (&a)[2 * KS], const h16x8 *__restrict__ db, int64_t tile, int lane) {
@@ -20,7 +21,7 @@ __device__ __forceinline__ void ld_tile(h16x8 (&a)[2 * KS], const h16x8 *__restr
 #pragma unroll
   for (int p = 0; p < 2 * KS; p++) a[p] = src[TileFmt<KS>::off(p, lane)];
 }
-// the hi pieces (2s) of a tile only: half its bytes (k3p_variant 22 / 23)
+// the hi pieces (2s) of a tile only: half its bytes (k3p_variant 22)
 template <int KS>
 __device__ __forceinline__ void ld_hi(h16x8 (&h)[KS], const h16x8 *__restrict__ db, int64_t tile, int lane) {
   const h16x8 *src = db + tile * TileFmt<KS>::STRIDE;
@@ -49,14 +50,8 @@ __device__ __forceinline__ void ld_hi(h16x8 (&h)[KS], const h16x8 *__restrict__ 
 //    read only packed values built by VALU code from the accumulators (k3h_pack), whose MFMA hazard
 //    the compiler already padded.
 typedef unsigned v4u32 __attribute__((ext_vector_type(4)));  // 16-B buffer store payload
-#define IA_HSLOT 224  // h16x8 per ring slot (3.5 KiB)
-static_assert(3 * 1024 + 512 == IA_HSLOT * 16, "a slot holds pieces 0, 2, 4 (1 KiB each) and the compact piece 6");
 __device__ __forceinline__ void dma16(const void *g, unsigned lds_addr) {
-#ifdef IA_EXP_DMA_NT  // experiment: the hi stream's DMAs with the non-temporal policy
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt" ::"s"(lds_addr), "v"(g) : "memory", "m0");
-#else
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(g) : "memory", "m0");
-#endif
 }
 template <int KS>
 __device__ __forceinline__ void dma_hi(const h16x8 *__restrict__ db, int64_t tile, h16x8 *slot, int lane) {
@@ -98,25 +93,15 @@ __device__ unsigned long long k3p_prof[24];
 // accumulators) so it fills MFMA shadow, walking the pair's two queries in lockstep (two
 // independent chains).
 //
-// Epilogue (per lane and query: best value b1 with its DB position, runner-up value b2):
-//   PK = false: per value v (4 VALU): c = v < b1;  b2 = med3(b1, b2, v);  b1 = c ? v : b1;
-//               i1 = c ? row : i1.
-//   PK = true (packed index, 3 VALU per value): the value's 4 low mantissa bits are replaced
-//               by its row index r within the lane's 16 rows of the tile (v_and_or_b32), so
-//               min/med3 on the packed floats carry the row along:  b2 = med3(b1, b2, pv);
-//               b1 = min(b1, pv); once per (query, tile): tile = (b1 changed) ? t : tile.
-//               A packed value differs from the MFMA value by < 16 ulp (<= 2^-19 |v|), which
-//               the certification bound includes (ia_eps_c_h(KS, true)).  f32 denormals are
-//               preserved (kernel FP mode), so packed tiny values keep their index bits.
+// Epilogue (per lane and query: best value b1 with its tile, runner-up value b2), packed index,
+// 3 VALU per value: the value's 4 low mantissa bits are replaced by its row index r within the
+// lane's 16 rows of the tile (v_and_or_b32), so min/med3 on the packed floats carry the row
+// along:  b2 = med3(b1, b2, pv);  b1 = min(b1, pv); once per (query, tile): tile = (b1 changed) ?
+// t : tile.  A packed value differs from the MFMA value by < 16 ulp (<= 2^-19 |v|), which the
+// certification bound includes (ia_eps_c_h(KS, true)).  f32 denormals are preserved (kernel FP
+// mode), so packed tiny values keep their index bits.
 // The per-lane subsets (lane half x wave) are merged through LDS into one record per query:
 // the top-2 list and the threshold T (every unlisted row of the chunk has value >= T).
-template <int QT>
-__device__ __forceinline__ void k3h_upd(float v, int row, int q, float (&b1)[QT], float (&b2)[QT], int (&i1)[QT]) {
-  const bool c = v < b1[q];
-  b2[q] = __builtin_amdgcn_fmed3f(b1[q], b2[q], v);
-  b1[q] = c ? v : b1[q];
-  i1[q] = c ? row : i1[q];
-}
 // med3 / min on packed values: single instructions (no canonicalising v_max on bit-built
 // operands; the packed operands are never MFMA results, so no MFMA read hazard is hidden)
 __device__ __forceinline__ float k3h_med3(float a, float b, float c) {
@@ -133,42 +118,32 @@ __device__ __forceinline__ float k3h_pack(float v, int r) {
   return __uint_as_float((__float_as_uint(v) & ~15u) | (unsigned)r);
 }
 
-template <int QT, bool PK>
-__device__ __forceinline__ void k3h_epi2(const f32x16 &e0, const f32x16 &e1, int q0, bool has1, int rb, int t,
-                                         float (&b1)[QT], float (&b2)[QT], int (&i1)[QT]) {
-  if constexpr (PK) {
-    const float o0 = b1[q0], o1 = has1 ? b1[q0 + 1] : 0.f;
+// packed epilogue of two accumulators into the queries q0 (and q0 + 1 when has1) of tile t
+template <int QT>
+__device__ __forceinline__ void k3h_epi2(const f32x16 &e0, const f32x16 &e1, int q0, bool has1, int t, float (&b1)[QT],
+                                         float (&b2)[QT], int (&i1)[QT]) {
+  const float o0 = b1[q0], o1 = has1 ? b1[q0 + 1] : 0.f;
 #pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const float p0 = k3h_pack(e0[r], r);
-      b2[q0] = k3h_med3(b1[q0], b2[q0], p0);
-      b1[q0] = k3h_min(b1[q0], p0);
-      if (has1) {
-        const float p1 = k3h_pack(e1[r], r);
-        b2[q0 + 1] = k3h_med3(b1[q0 + 1], b2[q0 + 1], p1);
-        b1[q0 + 1] = k3h_min(b1[q0 + 1], p1);
-      }
-    }
-    i1[q0] = b1[q0] != o0 ? t : i1[q0];
-    if (has1) i1[q0 + 1] = b1[q0 + 1] != o1 ? t : i1[q0 + 1];
-  } else {
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const int row = rb + (r & 3) + 8 * (r >> 2);
-      k3h_upd<QT>(e0[r], row, q0, b1, b2, i1);
-      if (has1) k3h_upd<QT>(e1[r], row, q0 + 1, b1, b2, i1);
+  for (int r = 0; r < 16; r++) {
+    const float p0 = k3h_pack(e0[r], r);
+    b2[q0] = k3h_med3(b1[q0], b2[q0], p0);
+    b1[q0] = k3h_min(b1[q0], p0);
+    if (has1) {
+      const float p1 = k3h_pack(e1[r], r);
+      b2[q0 + 1] = k3h_med3(b1[q0 + 1], b2[q0 + 1], p1);
+      b1[q0 + 1] = k3h_min(b1[q0 + 1], p1);
     }
   }
+  i1[q0] = b1[q0] != o0 ? t : i1[q0];
+  if (has1) i1[q0 + 1] = b1[q0 + 1] != o1 ? t : i1[q0 + 1];
 }
 
-// PROBE (diagnostic builds only, never selected by the product path): 1 = epilogue reduced to
-// one min per accumulator (MFMA + operand-load cost alone)
-template <int KS, int QT, int NW, bool PK, int PROBE = 0>
+template <int KS, int QT, int NW>
 __global__ void __launch_bounds__(NW * IA_WAVE, 1)
 k3h_scan(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, int n_tiles, int tpw, int qt0, int M, int nwg,
          int row0, int NT, float4 *__restrict__ rec, float *__restrict__ recT) {
   constexpr int NP = 2 * KS, NPAIR = (QT + 1) / 2, WGT = NW * IA_WAVE;
-  extern __shared__ h16x8 ldsh[];  // QT * NP * 64 (queries), reused for the merge
+  extern __shared__ h16x8 ldsh[];  // the queries (k3h_frag_bytes), reused for the merge (k3h_red_bytes)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
   const int wg = blockIdx.x;
   const int t_begin = wg * tpw, t_end = min(n_tiles, t_begin + tpw);
@@ -183,7 +158,7 @@ k3h_scan(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, int n_tiles
   __syncthreads();
 
   float b1[QT], b2[QT];
-  int i1[QT];  // PK = false: DB position of b1;  PK = true: tile of b1
+  int i1[QT];  // tile of b1
 #pragma unroll
   for (int q = 0; q < QT; q++) {
     b1[q] = FLT_MAX;
@@ -195,7 +170,6 @@ k3h_scan(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, int n_tiles
     {  // prefetch the next tile of this wave (clamped: always issue, never branch per load)
       ld_tile<KS>(an, db, min(t + NW, n_tiles - 1), lane);
     }
-    const int rbase = row0 + t * IA_TILE + 4 * half;
     asm volatile("" ::: "memory");  // LDS query fragments are re-read per tile, not hoisted
     f32x16 e0, e1;
 #pragma unroll
@@ -216,32 +190,26 @@ k3h_scan(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, int n_tiles
         c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], x0h, c0, 0, 0, 0);
         if (two) c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], x1h, c1, 0, 0, 0);
       }
-      if constexpr (PROBE == 1) {
-        b1[2 * qp] = fminf(b1[2 * qp], c0[qp & 15]);
-        if (two) b1[2 * qp + 1] = fminf(b1[2 * qp + 1], c1[qp & 15]);
-      } else {
-        if (qp >= 1) k3h_epi2<QT, PK>(e0, e1, 2 * qp - 2, true, rbase, t, b1, b2, i1);
-        e0 = c0;
-        e1 = c1;
-      }
+      if (qp >= 1) k3h_epi2<QT>(e0, e1, 2 * qp - 2, true, t, b1, b2, i1);
+      e0 = c0;
+      e1 = c1;
     }
-    if constexpr (PROBE == 0) k3h_epi2<QT, PK>(e0, e1, 2 * (NPAIR - 1), 2 * NPAIR - 1 < QT, rbase, t, b1, b2, i1);
+    k3h_epi2<QT>(e0, e1, 2 * (NPAIR - 1), 2 * NPAIR - 1 < QT, t, b1, b2, i1);
   };
   for (; t < t_end; t += 2 * NW) {
     body(a, an, t);
     if (t + NW >= t_end) break;
     body(an, a, t + NW);
   }
-  if constexpr (PK) {  // tile + packed in-tile index -> DB position
 #pragma unroll
-    for (int q = 0; q < QT; q++) {
-      const int r = (int)(__float_as_uint(b1[q]) & 15u);
-      i1[q] = b1[q] == FLT_MAX ? 0x7fffffff : row0 + i1[q] * IA_TILE + 4 * half + (r & 3) + 8 * (r >> 2);
-    }
+  for (int q = 0; q < QT; q++) {  // tile + packed in-tile index -> DB position
+    const int r = (int)(__float_as_uint(b1[q]) & 15u);
+    i1[q] = b1[q] == FLT_MAX ? 0x7fffffff : row0 + i1[q] * IA_TILE + 4 * half + (r & 3) + 8 * (r >> 2);
   }
 
   // ---- merge the 2*NW subsets of each query: lane halves by shuffle, waves through LDS
   __syncthreads();
+  static_assert(NW == K3H_NW, "the LDS format (ia_k3p_lds.h) is for this");
   Top2 *red = reinterpret_cast<Top2 *>(ldsh);  // [NW][QT][32]
 #pragma unroll
   for (int q = 0; q < QT; q++) {
@@ -345,7 +313,7 @@ __device__ __forceinline__ void k3p_pairs(const h16x8 (&a)[2 * KS], const h16x8 
       if (m2 == 3u) {
         f32x16 c0, c1;
         k3p_chain2<KS>(a, qb0, qb0 + NP * IA_WAVE, c0, c1);
-        k3h_epi2<QT, true>(c0, c1, q0, true, 0, t, b1, b2, i1);
+        k3h_epi2<QT>(c0, c1, q0, true, t, b1, b2, i1);
       } else if (m2 != 0u) {
         const bool sel = m2 == 2u;
         const f32x16 c = k3p_chain<KS>(a, sel ? qb0 + NP * IA_WAVE : qb0);
@@ -369,7 +337,7 @@ __device__ __forceinline__ void k3p_pairs(const h16x8 (&a)[2 * KS], const h16x8 
   }
 }
 
-// HHF (k3p_variant 14 / 15): each needed (DB tile, query tile) block first runs the hi x hi
+// The hi x hi block filter: each needed (DB tile, query tile) block first runs the hi x hi
 // product alone (4 MFMAs); its full product (12 MFMAs) and the top-2 epilogue follow only when
 // some value of the block can lie within its query's bound:
 //     c_hh <= lim_q = z_q + R_t (w_q + R_t 2^-9 + 2^-20)
@@ -396,7 +364,7 @@ __device__ __forceinline__ float k3p_min16(const f32x16 &c) {
   const float m4 = fminf(fminf(c[12], c[13]), c[14]);
   return fminf(fminf(fminf(m0, m1), fminf(m2, m3)), fminf(m4, c[15]));
 }
-// HHX = 3 (k3p_variant 22 / 23): the same filter on a hi-only tile buffer (ld_hi); the blocks
+// k3p_variant 22: the same filter on a hi-only tile buffer (ld_hi); the blocks
 // that pass run their full chains one tile later, from the whole tile loaded only then
 template <int KS, int QT, int Q>
 __device__ __forceinline__ void k3p_hhpipe_h(const h16x8 (&h)[KS], const h16x8 *lq, unsigned msk, float rt,
@@ -520,7 +488,7 @@ __device__ __forceinline__ void k3p_pairs_hl(const h16x8 (&a)[2 * KS], const h16
       if (m2 == 3u) {
         f32x16 c0, c1;
         k3p_chain2_hl<KS>(a, qh + q0 * QS, ql + q0 * QS, qh + q1 * QS, ql + q1 * QS, c0, c1);
-        k3h_epi2<QT, true>(c0, c1, q0, true, 0, t, b1, b2, i1);
+        k3h_epi2<QT>(c0, c1, q0, true, t, b1, b2, i1);
       } else if (m2 != 0u) {
         const bool sel = m2 == 2u;
         const int qq = sel ? q1 : q0;
@@ -545,7 +513,7 @@ __device__ __forceinline__ void k3p_pairs_hl(const h16x8 (&a)[2 * KS], const h16
   }
 }
 
-// HHX paired (k3p_variant 20 / 21): the same fused corrections, organised like k3p_pairs - the
+// k3p_variant 20 / 21: the filter with fused corrections, organised like k3p_pairs - the
 // hi x hi chains of a query-tile pair run as two independent chains, both bound tests follow,
 // and the passing blocks' corrections run as two chains (both pass) or one, with the two-query
 // epilogue when both pass.  Two independent MFMA chains per pair instead of k3p_hhfuse's
@@ -587,7 +555,7 @@ __device__ __forceinline__ void k3p_hhpairs(const h16x8 (&a)[2 * KS], const h16x
             c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], qb0[(2 * s + 1) * IA_WAVE], c0, 0, 0, 0);
             c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], qb1[(2 * s + 1) * IA_WAVE], c1, 0, 0, 0);
           }
-          k3h_epi2<QT, true>(c0, c1, q0, true, 0, t, b1, b2, i1);
+          k3h_epi2<QT>(c0, c1, q0, true, t, b1, b2, i1);
         } else if (p0) {
           k3p_corr<KS>(a, qb0, c0);
           k3p_epi1(c0, t, b1[q0], b2[q0], i1[q0]);
@@ -631,83 +599,62 @@ __device__ __forceinline__ void k3p_hhpairs(const h16x8 (&a)[2 * KS], const h16x
 #if defined(IA_K3H_KS) && defined(IA_K3H_QT)
 #define IA_K3H_CAT2(a, b, c) a##b##_##c
 #define IA_K3H_CAT(a, b, c) IA_K3H_CAT2(a, b, c)
-// variant (option "k3_variant"): 0 = compare/select epilogue, 1 = packed-index epilogue
-// The product library holds only the packed-index epilogue (variant 1); the compare/select
-// epilogue (0) and the probes (2, 3) are in git history.
-k3h_fn IA_K3H_CAT(ia_k3h_get_, IA_K3H_KS, IA_K3H_QT)(int variant) {
-  (void)variant;
-  return k3h_scan<IA_K3H_KS, IA_K3H_QT, IA_WGH / IA_WAVE, true>;
-}
+// the scan instance of this (KS, QT) object (option "k3_variant" 1, the packed-index epilogue)
+k3h_fn IA_K3H_CAT(ia_k3h_get_, IA_K3H_KS, IA_K3H_QT)() { return k3h_scan<IA_K3H_KS, IA_K3H_QT, K3H_NW>; }
 #endif
 
 // ------------------------------------------------------------------------------------------
-// K3p (k3p_variants 7, 11, 14, 15, 18..21).  Same pairs, same records semantics
-// as V1, organised so no phase waits on another's memory latency:
-//   1. ONE global round: every query's pruning record (thread = query, registers), the step's
-//      unsorted split-f16 query fragments (coalesced, registers), the workgroup's tile boxes
-//      (to LDS) and each wave's speculative first DB tile (PRE: this launch's presorted slice
-//      straight into LDS)
-//   2. bitonic sort by unique key; fragments and records scattered to their sorted LDS slots;
-//      query-tile boxes by 32-lane butterflies (PRE: skipped, or only the boxes)
-//   3. tiles handed out through an LDS counter; per tile the coarse (query-tile box) and fine
-//      (per query) need tests, the needed tile's load in flight while the previous one is
-//      contracted (two register buffers in rotation)
-//   4. per-query records exactly as V1
-// (The other versions of DESIGN.md §4b's progression - no interleaving, one or three tile
-// buffers, software-pipelined single chains, the previous step's order, the rotated-DB head
-// filter - are in the history of this file up to round 3.)
+// K3p, the certified pruned scan (k3h_prune3).  One workgroup = one block of QT
+// query tiles against one chunk of the DB's tiles.  Its phases, in the order of the body:
+//   block decode        which query block and DB chunk this workgroup is (XCD-aware)
+//   input wait          owner-computes steps only: the block's inputs come from another rank
+//   front end           PRE: this launch's presorted slice straight into LDS (k_query_sort sorted
+//                       the step once: qf / qinfo in sorted order, ord_in slot -> query, tbox the
+//                       sorted query tiles' boxes); otherwise ONE global round (every query's
+//                       pruning record and the unsorted fragments into registers, the chunk's
+//                       tile boxes into LDS), a sort by unique key in LDS (rank count or bitonic
+//                       network) and the scatter to sorted slots
+//   query-tile boxes    32-lane butterflies over the sorted slots (PRE: only when tbox is absent)
+//   tile walk           tiles handed out through an LDS counter; per tile the coarse (query-tile
+//                       box) and fine (per query) need tests, the hi x hi block filter
+//                       (c_hh <= lim_q, above) and the passing blocks' full products with the
+//                       packed top-2 epilogue.  Three stream forms (K3pStream, ia_k3p_lds.h)
+//   tile -> row         the packed (tile, in-tile index) of each lane's best -> DB row
+//   merge + store       the 2 NW subsets of each query merged through LDS; one record per query,
+//                       to its original slot (plain, write-through or owner-computes store)
+//   counters            the workgroup's pair / tile tallies (the pair slot holds
+//                       (pairs with corrections << 32) + box-needed pairs)
+// Block decode, query-tile boxes, tile -> row and counters are the k3p_* functions below; the
+// input waits, the front end, the three walks and merge + store stay in the body under "----"
+// markers with these names: as functions over shared views they cost registers (up to 20 VGPRs
+// and a wave of occupancy on the small-QT instances), which the 256-VGPR instances do not have.
+// Every LDS array's place and size is ia_k3p_lds.h's (shared with the launcher).
 // ------------------------------------------------------------------------------------------
-#define IA_K3P3_MAXQ 512   // queries per step (one per thread)
 // steps of up to IA_K3P_RANK_MAX queries are sorted by rank counting, wider ones by the bitonic
 // network (at 342 queries the network measured faster: profiles/r02/ab3, again in round 5:
 // profiles/r05/rank_sort)
 #define IA_K3P_RANK_MAX 256
-// PRE (k3p_variant 11, any Mpad <= 4096): the step's queries were sorted once by k_query_sort
-// (ia_prune.hip): qf / qinfo hold them in sorted order (fragments; lo, hi, (U', key) per slot),
-// ord_in maps a sorted slot to its query and tbox holds the sorted query tiles' boxes, so phase
-// 1 loads only this launch's slice and phase 2 (sort, scatter, tile boxes) is skipped.
-// HHF (k3p_variant 14 / 15): the hi x hi block filter above (k3p_hhpipe); the per-WG pair
-// counter slot then holds (pairs with corrections << 32) + box-needed pairs.  HHX: how the
-// correction products follow the filter (0: full chains, 1: fused single chains, 2: fused on
-// query-tile pairs, k3p_hhpairs).
-template <int KS, int QT, int NW, bool PRE = false, bool HHF = false, int HHX = 0>
-__global__ void __launch_bounds__(NW * IA_WAVE, 1)
-k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const float4 *__restrict__ qinfo,
-           const float4 *__restrict__ boxes, const int *__restrict__ pos2row, int NT, int qt0, int M, int Mpad, int nwg,
-           float4 *__restrict__ rec, float *__restrict__ recT, unsigned long long *__restrict__ pairs,
-           unsigned long long *__restrict__ tiles, int rev, const int *__restrict__ ord_in, int n_in,
-           int r0, int *__restrict__ ord_out, const float4 *__restrict__ tbox, const float *__restrict__ tnorm,
-           int nqb, int qt_end, XOScan xo) {
-  constexpr int NP = 2 * KS, NPAIR = (QT + 1) / 2, WGT = NW * IA_WAVE, NQ = QT * IA_TILE;
-  // unsorted fragments per thread (HHX 4: the hi pieces only)
-  constexpr int NE = PRE ? 1 : (IA_K3P3_MAXQ / IA_TILE * (HHX == 4 ? KS : NP) * IA_WAVE + WGT - 1) / WGT;
-  static_assert(QT <= 32 && 2 * NW >= QT, "need masks are 32-bit; one query tile per half wave");
-  // the in-kernel sort holds one query per thread; the tile walk takes any K (the launcher keeps
-  // K <= IA_K3P_MAXK_LDS: the boxes, need masks and R_t of the WG's tiles live in LDS)
-  static_assert(WGT >= IA_K3P3_MAXQ, "one query per thread");
-  static_assert(HHF && HHX >= 2 && HHX <= 4, "the product variants: 20 / 21 (HHX 2), 22 (3), 24 / 25 (4)");
-  extern __shared__ h16x8 ldsh[];  // sorted query fragments [QT][NP][64], reused for the merge
-  // HHX 4: ldsh holds the hi pieces only ([QT][KS][64]); the waves' LDS-DMA rings of the hi
-  // stream ([NW][3] slots of 3.5 KiB; the lo pieces in the second pass) are a static array of
-  // their own, so the compiler can tell that no other LDS access aliases a pending DMA (it puts
-  // a vmcnt(0) before any LDS access it cannot prove disjoint from one)
-  constexpr int QFP = HHX == 4 ? KS : NP;
-  __shared__ h16x8 ring[HHX == 4 ? NW * 3 * IA_HSLOT : 1];
-  float4 *qlo = reinterpret_cast<float4 *>(ldsh + QT * QFP * IA_WAVE);  // [NQ]
-  float4 *qhi = qlo + NQ;                                               // [NQ]
-  float *qU = reinterpret_cast<float *>(qhi + NQ);                     // [NQ]
-  float4 *tlo = reinterpret_cast<float4 *>(qU + NQ);                   // [QT] query-tile boxes
-  float4 *thi = tlo + QT;                                               // [QT]
-  float *tU = reinterpret_cast<float *>(thi + QT);                     // [QT]
-  unsigned *skey = reinterpret_cast<unsigned *>(tU + ((QT + 3) & ~3));  // [Mpad]   (PRE: [NQ] slice order)
-  int *order = reinterpret_cast<int *>(skey + (PRE ? NQ : Mpad));       // [Mpad] sorted -> query
-  int *rankof = order + (PRE ? 0 : Mpad);                               // [Mpad] query -> sorted
-  // PRE launches may cover several query blocks (nqb > 1): a grid of nqb x nwg workgroups, block
-  // b = the presorted query tiles [qt0 + b QT, min(qt0 + (b + 1) QT, qt_end)) against the DB
-  // chunk wg (tiles wg + nwg k), so one launch streams the DB once per block instead of one
-  // launch per block paying the setup and tail again.  When nwg is a multiple of 8 the blocks of
-  // one chunk get workgroup ids equal mod 8, i.e. the same XCD (round-robin dispatch): they read
-  // the same tiles at about the same time through one L2.
+// the launch block: which query block and DB chunk this workgroup is
+struct K3pBlk {
+  int wg, qblk;  // DB chunk, query block
+  int qt0, qtb;  // the block's first query tile and its tiles (PRE: the last block may hold fewer)
+  int K;         // tiles wg + nwg*k, k < K (host: nwg <= NT, K <= IA_K3P_MAXK_LDS)
+  int nwg;
+  // rev: this step walks the workgroup's tiles in reverse (alternate steps: the tiles read last
+  // by one step are read first by the next, while they are still in the memory-side cache)
+  int rev;
+  __device__ __forceinline__ int tk(int k) const { return wg + nwg * (rev ? K - 1 - k : k); }
+};
+// ---- block decode.  PRE launches may cover several query blocks (nqb > 1): a grid of nqb x nwg
+// workgroups, block b = the presorted query tiles [qt0 + b QT, min(qt0 + (b + 1) QT, qt_end))
+// against the DB chunk wg (tiles wg + nwg k), so one launch streams the DB once per block
+// instead of one launch per block paying the setup and tail again.  When nwg is a multiple of 8
+// the blocks of one chunk get workgroup ids equal mod 8, i.e. the same XCD (round-robin
+// dispatch): they read the same tiles at about the same time through one L2.
+template <int KS, int QT, bool PRE>
+__device__ __forceinline__ K3pBlk k3p_decode(int qt0, int nqb, int nwg, int NT, int Mpad, int qt_end, int rev, const XOScan &xo,
+                                             const h16x8 *__restrict__ &qf, const float4 *__restrict__ &qinfo) {
+  constexpr int NP = 2 * KS;
   int wg = blockIdx.x, qblk = 0;
   if ((PRE || xo.on) && nqb > 1) {
     if ((nwg & 7) == 0) {
@@ -724,21 +671,133 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     qf += (int64_t)qblk * (Mpad / IA_TILE) * NP * IA_WAVE;
     qinfo += 3 * (int64_t)qblk * Mpad;
   }
-  const int qtb = PRE ? min(QT, qt_end - qt0) : QT;  // query tiles of this block (PRE: the last may hold fewer)
-  const int K = (NT - wg + nwg - 1) / nwg;  // tiles wg + nwg*k, k < K (host: nwg <= NT, K <= IA_K3P_MAXK_LDS)
-  // rev: this step walks the workgroup's tiles in reverse (alternate steps: the tiles read last
-  // by one step are read first by the next, while they are still in the memory-side cache)
-  auto tk = [&](int k) { return wg + nwg * (rev ? K - 1 - k : k); };
-  float4 *wbox = reinterpret_cast<float4 *>(rankof + (PRE ? 0 : Mpad));  // [2K] the WG's tile boxes
-  unsigned *kmask = reinterpret_cast<unsigned *>(wbox + 2 * K);        // [K] need mask per tile
-  int *items = reinterpret_cast<int *>(kmask + K);                     // [K] needed tiles, in order
-  float *qzt = reinterpret_cast<float *>(items + K);                    // HHF: [NQ] z per sorted slot
-  float *qzw = qzt + NQ;                                                // HHF: [NQ] w per sorted slot
-  float *wR = qzw + NQ;                                                 // HHF: [K] R_t of the WG's tiles
-  int *plk = reinterpret_cast<int *>(wR + K);                           // HHX 4: [K] filter-passing tiles
-  unsigned *plm = reinterpret_cast<unsigned *>(plk + K);                // HHX 4: [K] their passing blocks
+  return K3pBlk{wg, qblk, qt0, PRE ? min(QT, qt_end - qt0) : QT, (NT - wg + nwg - 1) / nwg, nwg, rev};
+}
+
+// ---- query-tile boxes (min lo, max hi, max U' over the tile's real queries) by 32-lane
+// butterflies over the sorted slots in LDS: the in-kernel-sort path, and the presorted path
+// when the step was sorted by its gathers (option "fuse_sort": no k_query_sort, tbox = nullptr)
+template <int QT>
+__device__ __forceinline__ void k3p_tile_boxes(const float4 *qlo, const float4 *qhi, const float *qU, float4 *tlo, float4 *thi,
+                                               float *tU, int wave, int half, int lane) {
+  const int j = 2 * wave + half, x = j * IA_TILE + (lane & 31);
+  float4 lo = make_float4(INFINITY, INFINITY, INFINITY, INFINITY), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  float u = -INFINITY;
+  if (j < QT && qU[x] != -INFINITY) {  // padding slots (U' = -inf) never widen a box
+    lo = qlo[x];
+    hi = qhi[x];
+    u = qU[x];
+  }
+#pragma unroll
+  for (int o = 1; o < 32; o <<= 1) {
+    lo.x = fminf(lo.x, xlane_xor_f(lo.x, o));
+    lo.y = fminf(lo.y, xlane_xor_f(lo.y, o));
+    lo.z = fminf(lo.z, xlane_xor_f(lo.z, o));
+    lo.w = fminf(lo.w, xlane_xor_f(lo.w, o));
+    hi.x = fmaxf(hi.x, xlane_xor_f(hi.x, o));
+    hi.y = fmaxf(hi.y, xlane_xor_f(hi.y, o));
+    hi.z = fmaxf(hi.z, xlane_xor_f(hi.z, o));
+    hi.w = fmaxf(hi.w, xlane_xor_f(hi.w, o));
+    u = fmaxf(u, xlane_xor_f(u, o));
+  }
+  if ((lane & 31) == 0 && j < QT) {
+    tlo[j] = lo;
+    thi[j] = hi;
+    tU[j] = u;
+  }
+}
+
+// ---- tile -> row: the lane's (tile, packed in-tile index) of each query -> DB row
+template <int QT, bool TWO>
+__device__ __forceinline__ void k3p_rows(const float (&b1)[QT], int (&i1)[QT], int half, const int *__restrict__ pos2row,
+                                         const int *rowmap) {
+  if constexpr (TWO) {
+    // i1 holds WG-local tiles whose rows the second pass staged in LDS (every wave's)
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < QT; q++) {
+      const int r = (int)(__float_as_uint(b1[q]) & 15u);
+      i1[q] = b1[q] == FLT_MAX ? 0x7fffffff : rowmap[i1[q] * IA_TILE + 4 * half + (r & 3) + 8 * (r >> 2)];
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < QT; q++) {  // tile + packed in-tile index -> DB position (-> DB row)
+      const int r = (int)(__float_as_uint(b1[q]) & 15u);
+      const int pos = i1[q] * IA_TILE + 4 * half + (r & 3) + 8 * (r >> 2);
+      // the lane's candidate rows are looked up here, their loads in flight while the workgroup
+      // waits for its slowest wave and merges; the merge then orders ties by row instead of
+      // position (any order is exact: K4 reranks the listed rows and T bounds every other one)
+      i1[q] = b1[q] == FLT_MAX ? 0x7fffffff : pos2row[pos];
+    }
+  }
+}
+
+// ---- counters: the workgroup's own slots (stream-ordered launches: no atomics)
+template <int NW, K3pStream FORM>
+__device__ __forceinline__ void k3p_counters(const unsigned *wpairs, const unsigned *wtiles, const unsigned *wfull,
+                                             const unsigned *wtp, unsigned long long *__restrict__ pairs,
+                                             unsigned long long *__restrict__ tiles) {
+  unsigned long long sp = 0, st = 0, sf = 0, stp = 0;
+#pragma unroll
+  for (int w = 0; w < NW; w++) {
+    sp += wpairs[w];
+    st += wtiles[w];
+    sf += wfull[w];
+    stp += wtp[w];
+  }
+  pairs[blockIdx.x] += sp + (sf << 32);
+  tiles[blockIdx.x] += st + (stp << 32);  // (tiles with a filter-passing block << 32) + tiles loaded
+  // DB half-tiles loaded besides one per loaded tile (the algorithmic bytes):
+  // whole tiles: the lo half of each; hi-only stream: the lo halves of the passing tiles; two
+  // passes: the passing tiles again, whole
+  tiles[blockIdx.x + 2 * IA_NWG_H] += FORM == K3pStream::TwoPass ? 2 * stp : FORM == K3pStream::HiOnly ? stp : st;
+}
+
+template <int KS, int QT, int NW, bool PRE, K3pStream FORM>
+__global__ void __launch_bounds__(NW * IA_WAVE, 1)
+k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const float4 *__restrict__ qinfo,
+           const float4 *__restrict__ boxes, const int *__restrict__ pos2row, int NT, int qt0, int M, int Mpad, int nwg,
+           float4 *__restrict__ rec, float *__restrict__ recT, unsigned long long *__restrict__ pairs,
+           unsigned long long *__restrict__ tiles, int rev, const int *__restrict__ ord_in, int r0,
+           const float4 *__restrict__ tbox, const float *__restrict__ tnorm, int nqb, int qt_end, XOScan xo) {
+  constexpr int NP = 2 * KS, NPAIR = (QT + 1) / 2, WGT = NW * IA_WAVE, NQ = QT * IA_TILE;
+  constexpr bool TWO = FORM == K3pStream::TwoPass;
+  // unsorted fragments per thread (two passes: the hi pieces only)
+  constexpr int NE = PRE ? 1 : (IA_K3P3_MAXQ / IA_TILE * (TWO ? KS : NP) * IA_WAVE + WGT - 1) / WGT;
+  static_assert(QT <= 32 && 2 * NW >= QT, "need masks are 32-bit; one query tile per half wave");
+  // the in-kernel sort holds one query per thread; the tile walk takes any K (the launcher keeps
+  // K <= IA_K3P_MAXK_LDS: the boxes and R_t of the WG's tiles live in LDS)
+  static_assert(WGT >= IA_K3P3_MAXQ, "one query per thread");
+  static_assert(KS == IA_K3P_KS && NW == K3H_NW, "the LDS format (ia_k3p_lds.h) is for these");
+  extern __shared__ h16x8 ldsh[];  // K3pLds (ia_k3p_lds.h); its fragment area is reused for the merge
+  // two passes: the waves' LDS-DMA rings of the hi stream ([NW][3] slots of 3.5 KiB; the lo pieces
+  // in the second pass) are a static array of their own, so the compiler can tell that no other
+  // LDS access aliases a pending DMA (it puts a vmcnt(0) before any LDS access it cannot prove
+  // disjoint from one)
+  __shared__ h16x8 ring[TWO ? k3p_ring_h16x8() : 1];
+  // ---- block decode
+  const K3pBlk blk = k3p_decode<KS, QT, PRE>(qt0, nqb, nwg, NT, Mpad, qt_end, rev, xo, qf, qinfo);
+  const int wg = blk.wg, qblk = blk.qblk, qtb = blk.qtb, K = blk.K;
+  qt0 = blk.qt0;
+  auto tk = [&](int k) { return blk.tk(k); };
+  // ---- the LDS arrays (sizes and overlays: ia_k3p_lds.h)
+  const K3pLds lay = k3p_lds(QT, PRE, FORM, Mpad, K);
+  char *const lb = reinterpret_cast<char *>(ldsh);
+  float4 *qlo = reinterpret_cast<float4 *>(lb + lay.qlo), *qhi = reinterpret_cast<float4 *>(lb + lay.qhi);
+  float *qU = reinterpret_cast<float *>(lb + lay.qU);
+  float4 *tlo = reinterpret_cast<float4 *>(lb + lay.tlo), *thi = reinterpret_cast<float4 *>(lb + lay.thi);
+  float *tU = reinterpret_cast<float *>(lb + lay.tU);
+  unsigned *skey = reinterpret_cast<unsigned *>(lb + lay.skey);
+  int *order = reinterpret_cast<int *>(lb + lay.order), *rankof = reinterpret_cast<int *>(lb + lay.rankof);
+  float4 *wbox = reinterpret_cast<float4 *>(lb + lay.wbox);
+  float *qzt = reinterpret_cast<float *>(lb + lay.qzt), *qzw = reinterpret_cast<float *>(lb + lay.qzw);
+  float *wR = reinterpret_cast<float *>(lb + lay.wR);
+  int *plk = reinterpret_cast<int *>(lb + lay.plk);
+  unsigned *plm = reinterpret_cast<unsigned *>(lb + lay.plm);
   __shared__ unsigned wpairs[NW], wtiles[NW], wfull[NW], wtp[NW];
-  __shared__ int pcount, pctr;  // HHX 4: passing tiles listed / handed out
+  __shared__ int pcount, pctr;  // two passes: passing tiles listed / handed out
+  __shared__ int kctr;          // next tile index to hand out
+  static_assert(sizeof(ring) + 4 * sizeof(wpairs) + 3 * sizeof(int) <= k3p_static_bytes(FORM), "the static LDS the fit tests assume");
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int s0 = qt0 * IA_TILE;
@@ -746,13 +805,13 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
   K3P_T(ph[0]);
   const unsigned long long stamp0 = xo.stamp ? ia_clock() : 0ull;
 
-  // ---- 1. one global round
+  // ---- input wait and front end (PRE: the presorted slice; otherwise one global round)
   h16x8 a[NP], an[NP];
-  // HHX 4: the wave's first two tiles (static: wave, wave + NW) go to its ring speculatively (93 %
+  // two passes: the wave's first two tiles (static: wave, wave + NW) go to its ring speculatively (93 %
   // of the tiles are needed at 1024^2) once the global round's loads are in, so they are in
   // flight during the query sort (spec_hi below)
   h16x8 *wring = ring + wave * 3 * IA_HSLOT;
-  if constexpr (HHX != 4) ld_tile<KS>(a, db, tk(min(wave, K - 1)), lane);
+  if constexpr (!TWO) ld_tile<KS>(a, db, tk(min(wave, K - 1)), lane);
   if constexpr (PRE) {
     if (xo.on) {
       // owner-computes sharded step: this block's tiles come from their owner's K2s (another
@@ -775,7 +834,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     }
     // this launch's slice of the presorted queries, straight into LDS
     const h16x8 *qs = qf + (int64_t)qt0 * NP * IA_WAVE;
-    if constexpr (HHX == 4) {  // hi pieces only
+    if constexpr (TWO) {  // hi pieces only
       for (int e = tid; e < QT * KS * IA_WAVE; e += WGT) {
         const int pq = e >> 6, qt = pq / KS, s2 = pq - qt * KS;
         ldsh[e] = qt < qtb ? qs[(qt * NP + 2 * s2) * IA_WAVE + (e & 63)] : h16x8{};
@@ -790,10 +849,8 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       qhi[x] = ok ? qinfo[3 * sl + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
       const float4 u = ok ? qinfo[3 * sl + 2] : make_float4(-INFINITY, 0.f, -INFINITY, 0.f);
       qU[x] = u.x;
-      if constexpr (HHF) {
-        qzt[x] = u.z;
-        qzw[x] = u.w;
-      }
+      qzt[x] = u.z;
+      qzw[x] = u.w;
       skey[x] = ok ? ord_in[sl] : 0x7fffffff;  // slot -> query of this slice
     }
     if (tid < QT && tbox) {  // (tbox = nullptr: the boxes are taken from the slice below)
@@ -806,18 +863,17 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       const int t = tk(x);
       wbox[2 * x] = boxes[2 * t];
       wbox[2 * x + 1] = boxes[2 * t + 1];
-      if constexpr (HHF) wR[x] = tnorm[t];
+      wR[x] = tnorm[t];
     }
   }
   auto spec_hi = [&]() {
-    if constexpr (HHX == 4) {
+    if constexpr (TWO) {
       dma_hi<KS>(db, tk(min(wave, K - 1)), wring, lane);
       dma_hi<KS>(db, tk(min(wave + NW, K - 1)), wring + IA_HSLOT, lane);
     }
   };
-  __shared__ int kctr;  // next tile index to hand out
   if (tid == 0) {
-    kctr = HHX == 4 ? 2 * NW : NW;  // HHX 4: each wave's first two tiles are static (the speculative DMAs)
+    kctr = TWO ? 2 * NW : NW;  // two passes: each wave's first two tiles are static (the speculative DMAs)
     pcount = 0;
     pctr = 0;
   }
@@ -825,38 +881,8 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     __syncthreads();
     spec_hi();
   }
-  // the query-tile boxes (min lo, max hi, max U' over the tile's real queries) by 32-lane
-  // butterflies over the sorted slots in LDS: the in-kernel-sort path, and the presorted path
-  // when the step was sorted by its gathers (option "fuse_sort": no k_query_sort, tbox = nullptr)
-  auto tile_boxes = [&]() {
-    const int j = 2 * wave + half, x = j * IA_TILE + (lane & 31);
-    float4 lo = make_float4(INFINITY, INFINITY, INFINITY, INFINITY), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    float u = -INFINITY;
-    if (j < QT && qU[x] != -INFINITY) {  // padding slots (U' = -inf) never widen a box
-      lo = qlo[x];
-      hi = qhi[x];
-      u = qU[x];
-    }
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-      lo.x = fminf(lo.x, xlane_xor_f(lo.x, o));
-      lo.y = fminf(lo.y, xlane_xor_f(lo.y, o));
-      lo.z = fminf(lo.z, xlane_xor_f(lo.z, o));
-      lo.w = fminf(lo.w, xlane_xor_f(lo.w, o));
-      hi.x = fmaxf(hi.x, xlane_xor_f(hi.x, o));
-      hi.y = fmaxf(hi.y, xlane_xor_f(hi.y, o));
-      hi.z = fmaxf(hi.z, xlane_xor_f(hi.z, o));
-      hi.w = fmaxf(hi.w, xlane_xor_f(hi.w, o));
-      u = fmaxf(u, xlane_xor_f(u, o));
-    }
-    if ((lane & 31) == 0 && j < QT) {
-      tlo[j] = lo;
-      thi[j] = hi;
-      tU[j] = u;
-    }
-  };
-  if (PRE && !tbox) {
-    tile_boxes();
+  if (PRE && !tbox) {  // ---- query-tile boxes, from the slice
+    k3p_tile_boxes<QT>(qlo, qhi, qU, tlo, thi, tU, wave, half, lane);
     __syncthreads();
   }
   if constexpr (!PRE) {
@@ -886,21 +912,21 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     mzw = u.w;
     mkey = (__float_as_uint(u.y) & 0xFFFFF000u) | (unsigned)tid;  // unique (Mpad <= 4096)
   }
-  constexpr int NPL = HHX == 4 ? KS : NP;  // pieces per query tile loaded here (HHX 4: hi, 2s)
+  constexpr int NPL = TWO ? KS : NP;  // pieces per query tile loaded here (two passes: hi, 2s)
   const int ne = Mpad / IA_TILE * NPL * IA_WAVE;
   h16x8 qe[NE];
 #pragma unroll
   for (int i = 0; i < NE; i++) {
     int e = tid + WGT * i;
     e = e < ne ? e : 0;
-    if constexpr (HHX == 4) e = ((e >> 6) / KS * NP + 2 * ((e >> 6) % KS)) * IA_WAVE + (e & 63);
+    if constexpr (TWO) e = ((e >> 6) / KS * NP + 2 * ((e >> 6) % KS)) * IA_WAVE + (e & 63);
     qe[i] = qf[e];  // unconditional: equal vmcnt on every path
   }
   for (int x = tid; x < K; x += WGT) {
     const int t = tk(x);
     wbox[2 * x] = boxes[2 * t];
     wbox[2 * x + 1] = boxes[2 * t + 1];
-    if constexpr (HHF) wR[x] = tnorm[t];
+    wR[x] = tnorm[t];
   }
   if (tid < Mpad) {
     skey[tid] = mkey;
@@ -910,11 +936,11 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
   K3P_T(ph[1]);
   spec_hi();
 
-  // ---- 2. sort, scatter to sorted slots, query-tile boxes
+  // ---- front end, in-kernel sort: sort, scatter to sorted slots; query-tile boxes
   if (Mpad > IA_K3P_RANK_MAX) {  // (uniform) up to IA_K3P_RANK_MAX queries the rank count
     // bitonic network over the first 512 threads' unique keys (padding: 0xFFFFFFFF, last):
     // exchanges at distance < 64 are lane swaps, the 6 at distance >= 64 go through LDS (the
-    // query-fragment area, free until the scatter below)
+    // query-fragment area, free until the scatter below: k3p_bitonic_bytes)
     unsigned *sx = reinterpret_cast<unsigned *>(ldsh);
     unsigned v = mkey;
 #pragma unroll
@@ -948,10 +974,8 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
         qlo[x] = mlo;
         qhi[x] = mhi;
         qU[x] = mU;
-        if constexpr (HHF) {
-          qzt[x] = mzt;
-          qzw[x] = mzw;
-        }
+        qzt[x] = mzt;
+        qzw[x] = mzw;
       }
     }
   } else if (tid < Mpad) {
@@ -967,10 +991,8 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       qlo[x] = mlo;
       qhi[x] = mhi;
       qU[x] = mU;
-      if constexpr (HHF) {
-        qzt[x] = mzt;
-        qzw[x] = mzw;
-      }
+      qzt[x] = mzt;
+      qzw[x] = mzw;
     }
   }
   [[maybe_unused]] unsigned long long pa = 0, pb = 0, pc = 0;  // (phase probe stamps)
@@ -981,13 +1003,13 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
   for (int i = 0; i < NE; i++) {
     const int e = tid + WGT * i;
     if (e < ne) {
-      const int L = e & 63, pq = e >> 6, tq = pq / NPL, p = pq - tq * NPL;  // (HHX 4: p = hi piece s)
+      const int L = e & 63, pq = e >> 6, tq = pq / NPL, p = pq - tq * NPL;  // (two passes: p = hi piece s)
       const int x = rankof[tq * IA_TILE + (L & 31)] - s0;
       if (x >= 0 && x < NQ) ldsh[((x >> 5) * NPL + p) * IA_WAVE + (L & 32) + (x & 31)] = qe[i];
     }
   }
   K3P_T(pc);
-  tile_boxes();
+  k3p_tile_boxes<QT>(qlo, qhi, qU, tlo, thi, tU, wave, half, lane);
   [[maybe_unused]] unsigned long long pd = 0, pe = 0;
   K3P_T(pd);
   __syncthreads();
@@ -1015,7 +1037,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
   unsigned cnt = 0, ntl = 0, nfull = 0, ntp = 0;  // ntp: DB tiles with a filter-passing block
   {
     K3P_T(ph[3]);
-    // ---- 3'/4'. need tests interleaved with the contraction: wave v walks tiles k = v mod NW;
+    // ---- tile walk.  Need tests interleaved with the contraction: wave v walks tiles k = v mod NW;
     // while tile k is contracted, the next needed tile's load is in flight and the need tests
     // after it run on the VALU (two buffers in rotation)
     const bool cl = lane < QT;
@@ -1054,8 +1076,8 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       m = 0;
       return K;
     };
-    if constexpr (HHX == 4) {
-    // ---- k3p_variant 24 / 25: two passes over the workgroup's tiles.
+    if constexpr (TWO) {
+    // ---- tile walk, two passes (k3p_variant 24 / 25) over the workgroup's tiles.
     // (a) the hi stream: the hi halves (3.5 of 7 KiB per tile at KS = 4) by LDS-DMA into the
     //     wave's ring of three LDS slots, two tiles in flight while the third is filtered: per tile
     //     the hi x hi filter of its box-needed blocks (k3p_hhpipe_h on the slot); a tile with a
@@ -1218,7 +1240,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     // the DB rows of the passing tiles' positions, staged by the second pass behind the lo pieces
     // (rowmap[32 k + j] = pos2row of the WG's tile k, position j): the records' row lookups below
     // are then LDS reads instead of dependent global loads
-    int *rowmap = reinterpret_cast<int *>(ring + QT * KS * IA_WAVE);
+    int *rowmap = reinterpret_cast<int *>(ring + k3p_stage_lo_h16x8(QT));
     if (kcur < 0) {  // no passing tile of its own: the first from the pool
       const int j0 = grab2();
       if (j0 < npass) {
@@ -1262,8 +1284,8 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     } else {
     unsigned m;
     int k = next_k(wave, m);
-    if constexpr (HHX == 3) {
-    // ---- k3p_variant 22 / 23: the DB stream carries only the hi halves (3.5 of 7 KiB per tile
+    if constexpr (FORM == K3pStream::HiOnly) {
+    // ---- tile walk, hi-only stream (k3p_variant 22): the DB stream carries only the hi halves (3.5 of 7 KiB per tile
     // at KS = 4).  Per tile: the hi x hi filter of its box-needed blocks on a hi buffer (two in
     // rotation, the next tile's in flight); the tile's lo halves are then loaded only when a
     // block passed (its hi halves copied from the hi buffer; else the same load instructions at
@@ -1324,7 +1346,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       // makes the MFMAs below wait for the prefetch itself
       ld_tile<KS>(nxt, db, tk(kn < K ? kn : k), lane);
       asm volatile("" ::: "memory");  // LDS query fragments are re-read per tile, not hoisted
-      {  // HHX 2: the fused corrections on query-tile pairs
+      {  // the fused corrections on query-tile pairs
         unsigned pass = 0;
         k3p_hhpairs<KS, QT, 0>(cur, ldsh + lane, m, wR[k], qzt + (lane & 31), qzw + (lane & 31), tk(k), b1, b2, i1, pass);
         nfull += __popc(pass);
@@ -1340,32 +1362,14 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       if (k >= K) break;
       step(an, a);
     }
-    }  // HHX != 3
-    }  // HHX != 4
+    }  // whole tiles
+    }  // one pass
   }
   K3P_T(ph[4]);
-  if constexpr (HHX == 4) {
-    // i1 holds WG-local tiles whose rows the second pass staged in LDS (every wave's)
-    const int *rowmap = reinterpret_cast<const int *>(ring + QT * KS * IA_WAVE);
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < QT; q++) {
-      const int r = (int)(__float_as_uint(b1[q]) & 15u);
-      i1[q] = b1[q] == FLT_MAX ? 0x7fffffff : rowmap[i1[q] * IA_TILE + 4 * half + (r & 3) + 8 * (r >> 2)];
-    }
-  } else {
-#pragma unroll
-  for (int q = 0; q < QT; q++) {  // tile + packed in-tile index -> DB position (-> DB row)
-    const int r = (int)(__float_as_uint(b1[q]) & 15u);
-    const int pos = i1[q] * IA_TILE + 4 * half + (r & 3) + 8 * (r >> 2);
-    // the lane's candidate rows are looked up here, their loads in flight while the workgroup
-    // waits for its slowest wave and merges; the merge then orders ties by row instead of
-    // position (any order is exact: K4 reranks the listed rows and T bounds every other one)
-    i1[q] = b1[q] == FLT_MAX ? 0x7fffffff : pos2row[pos];
-  }
-  }  // HHX != 4
+  // ---- tile -> row
+  k3p_rows<QT, TWO>(b1, i1, half, pos2row, reinterpret_cast<const int *>(ring + k3p_stage_lo_h16x8(QT)));
 
-  // ---- 5. merge the 2*NW subsets of each query; records go to the original query slots
+  // ---- merge + store: the 2*NW subsets of each query merged; records go to the original query slots
   // (the slice's query order is read before the reduction area, which extends past the
   // fragments for NW = 16, overwrites it)
   const int mq_pre = tid < NQ ? (PRE ? (int)skey[tid] : order[s0 + tid]) : 0;
@@ -1377,12 +1381,12 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     wfull[wave] = nfull;
     wtp[wave] = ntp;
   }
-  Top2 *red = reinterpret_cast<Top2 *>(ldsh);  // [NW][QT][32], inside the query-fragment area
-  // HHX 4: every lane's subset (b1, b2 as T, row) goes to LDS as it stands
-  // ([NW][QT][64] per field) and the per-query merge takes 16 subsets: no half-wave merge
+  Top2 *red = reinterpret_cast<Top2 *>(ldsh);  // [NW][QT][32] (k3p_red_top2_bytes)
+  // two passes: every lane's subset (b1, b2 as T, row) goes to LDS as it stands
+  // ([NW][QT][64] per field, k3p_red_lanes_bytes) and the per-query merge takes 16 subsets: no half-wave merge
   float *rv1 = reinterpret_cast<float *>(ldsh), *rvT = rv1 + NW * QT * IA_WAVE;
   int *ri1 = reinterpret_cast<int *>(rvT + NW * QT * IA_WAVE);
-  constexpr bool T16 = HHX == 4;
+  constexpr bool T16 = TWO;
   if constexpr (T16) {
 #pragma unroll
     for (int q = 0; q < QT; q++) {
@@ -1466,22 +1470,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     }
   }
   K3P_T(ph[9]);
-  if (tid == 0) {  // the workgroup's own counter slots (stream-ordered launches: no atomics)
-    unsigned long long sp = 0, st = 0, sf = 0, stp = 0;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-      sp += wpairs[w];
-      st += wtiles[w];
-      sf += wfull[w];
-      stp += wtp[w];
-    }
-    pairs[blockIdx.x] += sp + (HHF ? sf << 32 : 0ull);
-    tiles[blockIdx.x] += st + (stp << 32);  // (tiles with a filter-passing block << 32) + tiles loaded
-    // DB half-tiles loaded besides one per loaded tile (the algorithmic bytes):
-    // whole tiles (HHX <= 2): the lo half of each; hi-only stream (3): the lo halves of the
-    // passing tiles; two passes (4): the passing tiles again, whole
-    tiles[blockIdx.x + 2 * IA_NWG_H] += HHX == 4 ? 2 * stp : HHX == 3 ? stp : st;
-  }
+  if (tid == 0) k3p_counters<NW, FORM>(wpairs, wtiles, wfull, wtp, pairs, tiles);
   if (xo.stamp) {  // (uniform) option "stamps": the workgroup's first and last tick
     __syncthreads();
     if (tid == 0) ia_stamp_wg(xo.stamp, stamp0);
@@ -1527,21 +1516,17 @@ void ia_k3p_probe_dump() {  // diagnostic build only: phase cycles per plateau w
 #endif
 
 #if defined(IA_K3H_KS) && defined(IA_K3H_QT)
-// pruned scan instance (1 channel only: KS = 4)
-// The product library holds the pruned scans of DESIGN.md §4b that are still selectable (the
-// earlier versions - no filter, single chains, v0-v19 and v23 - are in the history of this
-// file up to round 4): in-kernel query sort (steps of <= 512 queries) / presorted form.
+// The pruned scan instances of this (KS, QT) object (1 channel only: KS = 4), by option
+// "k3p_variant": an in-kernel query sort (steps of <= IA_K3P3_MAXQ queries) or a presorted front
+// end, times a stream form (ia_k3p_lds.h: k3p_variant_pre, k3p_variant_form).
 k3p_fn IA_K3H_CAT(ia_k3p_get_, IA_K3H_KS, IA_K3H_QT)(int variant) {
   if constexpr (IA_K3H_KS == 4) {
     constexpr int NW = IA_WGH / IA_WAVE;
-    // 20 / 21: whole tiles in two register buffers, the fused corrections on query-tile pairs
-    if (variant == 20) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, false, true, 2>;
-    if (variant == 21) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, true, true, 2>;
-    // 22: the filter on hi-only tile loads, full chains of the passing tiles one tile later
-    if (variant == 22) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, false, true, 3>;
-    // 24 / 25: a hi stream three tiles deep, then the passing tiles' full chains (two passes)
-    if (variant == 24) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, false, true, 4>;
-    if (variant == 25) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, true, true, 4>;
+    if (variant == 20) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, false, K3pStream::Whole>;
+    if (variant == 21) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, true, K3pStream::Whole>;
+    if (variant == 22) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, false, K3pStream::HiOnly>;
+    if (variant == 24) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, false, K3pStream::TwoPass>;
+    if (variant == 25) return k3h_prune3<IA_K3H_KS, IA_K3H_QT, NW, true, K3pStream::TwoPass>;
     return nullptr;
   } else {
     return nullptr;

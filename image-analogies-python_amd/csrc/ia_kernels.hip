@@ -38,9 +38,6 @@
 #define IA_PQ_WPB 1
 #endif
 #define IA_PQ_WG (IA_WAVE * IA_PQ_WPB)
-#ifndef IA_K4_RPL8
-#define IA_K4_RPL8 0  // 1: the fused merge always reads 8 records per lane (A/B builds)
-#endif
 #if IA_PROBE & 8  // diagnostic build only: s_memtime phase stamps of sampled merge waves
 #define IA_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); stamp[k] = __builtin_amdgcn_s_memtime(); \
                          __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -1407,12 +1404,7 @@ __device__ __forceinline__ void gather_p_query(const LevelGeo &g, const StepDesc
   if (qi > 0 && (lane < 15 || nnl)) {
     const int k = lane < 15 ? lane : lane - 15;
     const int nr = r - 2 + k / 5, nc = c - 2 + k % 5;
-#ifdef IA_EXP_NOABOVE  // experiment: U' without the row-above step-t neighbour's candidates
-    const bool skip_above = FUSE && nr == h.r1 && nc == h.c1;
-#else
-    const bool skip_above = false;
-#endif
-    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < qi && !skip_above) {
+    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < qi) {
       const int nb = nr * g.bw + nc;
       int sr = 0, sc = 0, si = 0, nnrow = -1;
       if (!nnl) {
@@ -2727,7 +2719,7 @@ int ia_k3_qtmax(int KH) { return KH == 28 ? 11 : KH == 56 ? 5 : 3; }
 // the default cap is 64 KiB), once per kernel.  Several host threads launch through one libia
 // (one context each: DeviceSweep, bench --streams), so the set is guarded; the attribute is the
 // arch maximum rather than the launch's size, so no thread can lower it under another's launch.
-static void allow_full_lds(const void *fn) {
+void ia_allow_full_lds(const void *fn) {
   static std::mutex mu;
   static std::unordered_set<const void *> done;
   std::lock_guard<std::mutex> lk(mu);
@@ -2744,7 +2736,7 @@ void ia_launch_k3(int KH, int qt, const float4 *db, const float4 *qf, int n_tile
   else if (KH == 56) fn = K3Table<56, 1, 2, 3, 4, 5>::get(qt);
   else fn = K3Table<84, 1, 2, 3>::get(qt);
   const size_t lds = (size_t)qt * (KH / 4) * IA_WAVE * sizeof(float4);
-  allow_full_lds((const void *)fn);
+  ia_allow_full_lds((const void *)fn);
   hipLaunchKernelGGL(fn, dim3(nwg), dim3(IA_WG), lds, st, db, qf, n_tiles, tpw, qt0, M, nwg, row0, NT, rec, recT);
 }
 
@@ -2754,7 +2746,7 @@ static void launch_merge_j(const LevelGeo &g, const StepDesc &sd, const Imgs &A,
   const dim3 grid(cdiv(sd.J * sd.M, IA_PQ_WPB));
   // the fused merge with 4 records per lane when the scan ran <= 256 workgroups (every
   // split-f16 scan): half the record loads and candidate tests of the 8-per-lane form
-  const bool r4 = FUSED && ma.nwg <= 4 * IA_WAVE && !IA_K4_RPL8;
+  const bool r4 = FUSED && ma.nwg <= 4 * IA_WAVE;
   if (jobs.J == 1) {
     if (r4)
       hipLaunchKernelGGL((k_merge_level<CH, FUSED, IMG, JobArg1, 4>), grid, dim3(IA_PQ_WG), 0, st, g, sd, A, ma, win, JobArg1{jobs.j0});
@@ -2919,10 +2911,6 @@ void ia_launch_coherence_batch(const double *pts, int64_t n, int d, const double
 double ia_k3h_tile_bytes(int KS) { return KS == 4 ? 16.0 * TileFmt<4>::STRIDE : KS == 7 ? 16.0 * TileFmt<7>::STRIDE : 0.; }
 int ia_ks_for(int ch) { return ch == 1 ? 4 : ch == 2 ? 7 : 0; }  // 3 channels: fp32 matcher
 int ia_k3h_qtmax(int KS) { return KS == 4 ? 11 : 8; }
-size_t ia_k3h_lds(int KS, int qt) {
-  const size_t q = (size_t)qt * 2 * KS * IA_WAVE * 16, m = (size_t)(IA_WGH / IA_WAVE) * qt * IA_TILE * sizeof(Top2);
-  return q > m ? q : m;
-}
 
 // microbenchmark operands: pseudo-random f16 values in [-0.5, 0.5) (hash of the index)
 __global__ void __launch_bounds__(IA_WG) k_fill_random_f16(_Float16 *__restrict__ p, int64_t n, unsigned seed) {
@@ -2997,99 +2985,3 @@ void ia_launch_gather_p(const LevelGeo &g, const StepDesc &sd, const Imgs &B, co
   launch_gather_p_t<false>(g, sd, B, jobs, mu, q64, qn2, qf, db64, basis, ufac, qinfo, A, x, st);
 }
 
-
-// split-f16 distance kernels live in ia_k3h.hip, compiled once per (KS, QT) instance
-#define IA_K3H_DECL(ks, qt) k3h_fn ia_k3h_get_##ks##_##qt(int variant);
-IA_K3H_DECL(4, 1) IA_K3H_DECL(4, 2) IA_K3H_DECL(4, 3) IA_K3H_DECL(4, 4) IA_K3H_DECL(4, 5) IA_K3H_DECL(4, 6)
-IA_K3H_DECL(4, 7) IA_K3H_DECL(4, 8) IA_K3H_DECL(4, 9) IA_K3H_DECL(4, 10) IA_K3H_DECL(4, 11)
-IA_K3H_DECL(7, 1) IA_K3H_DECL(7, 2) IA_K3H_DECL(7, 3) IA_K3H_DECL(7, 4) IA_K3H_DECL(7, 5) IA_K3H_DECL(7, 6)
-IA_K3H_DECL(7, 7) IA_K3H_DECL(7, 8)
-static k3h_fn k3h_get(int KS, int qt) {
-  typedef k3h_fn (*getter)(int);
-  static const getter g4[] = {ia_k3h_get_4_1, ia_k3h_get_4_2, ia_k3h_get_4_3, ia_k3h_get_4_4,  ia_k3h_get_4_5, ia_k3h_get_4_6,
-                              ia_k3h_get_4_7, ia_k3h_get_4_8, ia_k3h_get_4_9, ia_k3h_get_4_10, ia_k3h_get_4_11};
-  static const getter g7[] = {ia_k3h_get_7_1, ia_k3h_get_7_2, ia_k3h_get_7_3, ia_k3h_get_7_4,
-                              ia_k3h_get_7_5, ia_k3h_get_7_6, ia_k3h_get_7_7, ia_k3h_get_7_8};
-  return KS == 4 ? g4[qt - 1](1) : g7[qt - 1](1);  // the packed-index epilogue, the only one built
-}
-void ia_launch_k3h(int KS, int qt, const void *db, const void *qf, int n_tiles, int tpw, int qt0, int M, int nwg, int row0,
-                   int NT, float4 *rec, float *recT, hipStream_t st) {
-  const k3h_fn fn = k3h_get(KS, qt);
-  allow_full_lds((const void *)fn);
-  hipLaunchKernelGGL(fn, dim3(nwg), dim3(IA_WGH), ia_k3h_lds(KS, qt), st, (const h16x8 *)db, (const h16x8 *)qf, n_tiles, tpw,
-                     qt0, M, nwg, row0, NT, rec, recT);
-}
-
-// pruned split-f16 distance kernels (ia_k3h.hip k3h_prune, 1 channel)
-#define IA_K3P_DECL(qt) k3p_fn ia_k3p_get_4_##qt(int);
-IA_K3P_DECL(1) IA_K3P_DECL(2) IA_K3P_DECL(3) IA_K3P_DECL(4) IA_K3P_DECL(5) IA_K3P_DECL(6) IA_K3P_DECL(7) IA_K3P_DECL(8)
-IA_K3P_DECL(9) IA_K3P_DECL(10) IA_K3P_DECL(11)
-size_t ia_k3p_lds(int qt, int Mpad) {
-  const size_t NQ = (size_t)qt * IA_TILE;
-  const size_t qfrag = (size_t)qt * 8 * IA_WAVE * 16;  // KS = 4: NP = 8 h16x8 per lane
-  return qfrag + NQ * 36 + (size_t)qt * 32 + (size_t)((qt + 3) & ~3) * 4 + (size_t)Mpad * 8;
-}
-// The one place that decides which pruned-scan kernel a launch runs: from option "k3p_variant",
-// whether the queries arrive presorted and whether this is an owner-computes scan; then by what
-// fits.  fn = nullptr: the library holds no instance (ia_set_option accepts only built variants).
-struct K3pKernel {
-  k3p_fn fn;
-  size_t lds;  // dynamic LDS bytes
-};
-static K3pKernel k3p_kernel(int option, bool presorted, bool owner_scan, int qt, int Mpad, int kmax) {
-  typedef k3p_fn (*getter)(int);
-  static const getter g4[] = {ia_k3p_get_4_1, ia_k3p_get_4_2, ia_k3p_get_4_3, ia_k3p_get_4_4,  ia_k3p_get_4_5, ia_k3p_get_4_6,
-                              ia_k3p_get_4_7, ia_k3p_get_4_8, ia_k3p_get_4_9, ia_k3p_get_4_10, ia_k3p_get_4_11};
-  // the option's in-kernel-sort form (20 / 22 / 24) or its presorted form: 21, or the two-pass
-  // 25 under 24 / 25 (round 6, on the trimmed stream: cfg4 6.66 -> 6.91 M px/s against 21's whole
-  // tiles) - owner-computes scans take 25 only where it was asked for by name
-  int variant;
-  if (presorted) variant = option == 25 || (option == 24 && !owner_scan) ? 25 : 21;
-  else variant = option == 21 ? 20 : option == 25 ? 24 : option;
-  // the in-kernel sort holds <= 512 queries (the callers sort wider steps first, K2s); every
-  // variant walks any number of tiles (the host keeps kmax <= IA_K3P_MAXK_LDS)
-  if (!presorted && Mpad > 512) variant = 21;
-  const size_t NQ = (size_t)qt * IA_TILE;
-  auto dyn_lds = [&](int v) {
-    const bool pre = v == 21 || v == 25;
-    const size_t qfrag = (size_t)qt * (v >= 24 ? 4 : 8) * IA_WAVE * 16;  // v24 / 25: hi pieces only
-    size_t l = pre ? qfrag + NQ * 36 + (size_t)qt * 32 + (size_t)((qt + 3) & ~3) * 4 + NQ * 4 + (size_t)kmax * 40
-                   : ia_k3p_lds(qt, Mpad) - (size_t)qt * 8 * IA_WAVE * 16 + qfrag + (size_t)Mpad * 4 + (size_t)kmax * 40;
-    l += NQ * 8 + (size_t)kmax * 4;            // (z, w) per sorted query slot, R_t per tile
-    if (v >= 24) l += (size_t)kmax * 8;        // the filter-passing tiles and their blocks
-    size_t red = (size_t)(IA_WGH / IA_WAVE) * qt * IA_TILE * 20;  // the subset merge's Top2 area
-    if (v >= 24) red = std::max(red, (size_t)(IA_WGH / IA_WAVE) * qt * IA_WAVE * 12);  // (every lane's subset)
-    return l > red ? l : red;
-  };
-  if (variant >= 24) {  // the static LDS-DMA rings (86 KiB) + this launch's dynamic part must fit 160 KiB
-    hipFuncAttributes fa;
-    const k3p_fn f24 = g4[qt - 1](variant);
-    const size_t stat = f24 && hipFuncGetAttributes(&fa, (const void *)f24) == hipSuccess ? fa.sharedSizeBytes : 0;
-    // (and the second pass stages the lo pieces + a row map of the WG's tiles in the rings' 84 KiB)
-    const bool ring_fits = (size_t)qt * 4 * IA_WAVE * 16 + (size_t)kmax * IA_TILE * 4 <= (size_t)8 * 3 * 3584;
-    // (many tiles per workgroup or wide steps): the one-pass forms
-    if (!f24 || !ring_fits || stat + dyn_lds(variant) > 160 * 1024) variant = variant == 25 ? 21 : 22;
-  }
-  return {g4[qt - 1](variant), dyn_lds(variant)};
-}
-int ia_launch_k3p(const K3pLaunch &a, int option, bool presorted, hipStream_t st) {
-  const bool owner_scan = a.xo && a.xo->on;
-  const K3pKernel k = k3p_kernel(option, presorted, owner_scan, a.qt, a.Mpad, (a.NT + a.nwg - 1) / a.nwg);
-  // (a missing instance is an error the level reports, never a silently skipped scan whose stale
-  // records the merge would consume)
-  if (!k.fn) return -1;  // IA_EINVAL (include/ia.h)
-  // nqb > 1 (presorted kernels and owner-computes scans only): one launch of nqb query blocks x
-  // nwg DB chunks
-  const int nqb = presorted || owner_scan ? a.nqb : 1;
-  const int qt_end = nqb == 1 ? a.qt0 + a.qt : a.qt_end;
-  XOScan x{};  // off unless an owner-computes step passes its exchange
-  if (a.xo) x = *a.xo;
-  x.stamp = a.stamp;
-  x.rec_wt = a.rec_wt;
-  allow_full_lds((const void *)k.fn);
-  // (alternate steps walk in reverse; the kernel's n_in / ord_out arguments are unused)
-  hipLaunchKernelGGL(k.fn, dim3(nqb * a.nwg), dim3(IA_WGH), k.lds, st, (const h16x8 *)a.db, (const h16x8 *)a.qf, a.qinfo, a.boxes,
-                     a.pos2row, a.NT, a.qt0, a.M, a.Mpad, a.nwg, a.rec, a.recT, a.pairs, a.tiles, a.step & 1, a.order, 0, a.r0,
-                     nullptr, a.tbox, a.tnorm, nqb, qt_end, x);
-  return 0;
-}

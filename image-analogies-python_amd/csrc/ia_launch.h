@@ -1,9 +1,12 @@
-// ia_launch.h — host launchers of the kernels in ia_kernels.hip (used by ia_capi.cpp).
+// ia_launch.h — host launchers of the kernels in ia_kernels.hip, ia_prune.hip, ia_pyramid.hip and
+// ia_k3h.hip (the latter in ia_k3p_launch.hip); used by ia_capi.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "ia_internal.h"
 
+// allow a kernel the whole LDS of a CU as dynamic shared memory (once per kernel; thread-safe)
+void ia_allow_full_lds(const void *fn);
 void ia_launch_means(int ch, const Imgs &A, int n_ap, double *mu, hipStream_t st);
 void ia_launch_db_build(const LevelGeo &g, const Imgs &A, const double *mu, float4 *db, unsigned *Rbits, hipStream_t st);
 void ia_launch_gather(const LevelGeo &g, const StepDesc &sd, const Imgs &B, const JobSet &jobs, const double *mu, double *q64,
@@ -38,7 +41,6 @@ void ia_launch_coherence_batch(const double *pts, int64_t n, int d, const double
 int ia_ks_for(int ch);
 double ia_k3h_tile_bytes(int KS);  // HBM bytes of one split-f16 DB tile (TileFmt)
 int ia_k3h_qtmax(int KS);
-size_t ia_k3h_lds(int KS, int qt);
 void ia_launch_absmax(const double *const *p, const int64_t *n, unsigned *out, hipStream_t st);
 void ia_launch_db_build_h(const LevelGeo &g, const Imgs &A, const double *db64, const double *mu, void *db, unsigned *Rbits,
                           hipStream_t st);
@@ -64,12 +66,11 @@ void ia_launch_query_sort(const float4 *qinfo, const void *qf, int Mpad, int KS,
                           float4 *tbox, hipStream_t st);
 // owner-computes sharded step (exchange = 2): the owner's queries sorted into every rank's area
 void ia_launch_query_sort_xo(const float4 *qinfo, const void *qf, const XOSort &xs, hipStream_t st);
-size_t ia_k3p_lds(int qt, int Mpad);
 void ia_merge_gather_occupancy(int *vgprs, int *blocks_per_cu, int *wg_threads);
 // One pruned scan launch (ia_k3h.hip k3h_prune3).  The caller names option "k3p_variant" and
 // says whether the queries arrive presorted (K2s or the previous fused launch's gathers sorted
 // them: qf / qinfo / order / tbox are then k_query_sort's outputs); which kernel instance that
-// means for this launch is decided next to the launcher (ia_kernels.hip k3p_kernel).
+// means for this launch is decided next to the launcher (ia_k3p_launch.hip k3p_kernel).
 struct K3pLaunch {
   const void *db;              // the scanned DB slice: its first stored tile ...
   int NT;                      // ... and its tiles

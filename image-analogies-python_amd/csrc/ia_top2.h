@@ -77,7 +77,7 @@ __device__ __forceinline__ float xlane_xor_f(float v, int J) { return __uint_as_
 
 // split-f16 distance kernel entry (ia_k3h.hip)
 typedef void (*k3h_fn)(const h16x8 *, const h16x8 *, int, int, int, int, int, int, int, float4 *, float *);
-// pruned split-f16 distance kernel entry (ia_k3h.hip, k3h_prune)
+// pruned split-f16 distance kernel entry (ia_k3h.hip, k3h_prune3)
 typedef void (*k3p_fn)(const h16x8 *, const h16x8 *, const float4 *, const float4 *, const int *, int, int, int, int, int,
-                       float4 *, float *, unsigned long long *, unsigned long long *, int, const int *, int, int,
-                       int *, const float4 *, const float *, int, int, XOScan);
+                       float4 *, float *, unsigned long long *, unsigned long long *, int, const int *, int,
+                       const float4 *, const float *, int, int, XOScan);
