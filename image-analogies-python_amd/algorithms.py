@@ -15,7 +15,8 @@ Hot-path functions run on the GPU:
 
 compute_feature_array, extract_pixel_feature and compute_distance are kept as the reference's
 per-pixel/array helpers (host numpy over the caller's arrays) for code written against that API;
-the level path computes the same quantities on the GPU (K1/K2/K4 in csrc/ia_kernels.hip).
+the level path computes the same quantities on the GPU (K1 in csrc/ia_level_db.hip,
+K2 in csrc/ia_gather.hip, K4 in csrc/ia_kernels.hip).
 """
 import numpy as np
 

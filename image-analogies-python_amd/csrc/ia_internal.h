@@ -356,7 +356,7 @@ struct NextStep {
   unsigned long long *kslot;
   int prefetch;              // option "prefetch_next": the gathers' step-independent inputs load during the merge
   int early;                 // option "early_gather": the merge waves' gathers run everything but the row
-                             // above's feature before its handoff (ia_kernels.hip gather_p_early)
+                             // above's feature before its handoff (ia_gather.h gather_p_early)
   int *sorder;
   float4 *sinfo;
   void *sfrag;

@@ -1,6 +1,6 @@
 // ia_k3h.hip — K3h, the split-f16 MFMA distance scan of best_approximate_match
 // (algorithms.py:73-75): |a'|^2 - 2 q'.a' for every (DB row, query) of a wavefront step on
-// v_mfma_f32_32x32x16_f16 with hi/lo-split operands (ia_kernels.hip, "Split-f16 matcher"),
+// v_mfma_f32_32x32x16_f16 with hi/lo-split operands (ia_dev.h, "Split-f16 matcher"),
 // fused per-query top-2 + certification threshold.
 //
 // Compiled once per (KS, QT) instance (-DIA_K3H_KS, -DIA_K3H_QT; see Makefile) so the
@@ -341,7 +341,7 @@ __device__ __forceinline__ void k3p_pairs(const h16x8 (&a)[2 * KS], const h16x8 
 // product alone (4 MFMAs); its full product (12 MFMAs) and the top-2 epilogue follow only when
 // some value of the block can lie within its query's bound:
 //     c_hh <= lim_q = z_q + R_t (w_q + R_t 2^-9 + 2^-20)
-// where R_t >= max |a'| over the tile's rows and (z_q, w_q) come from K2p (ia_kernels.hip):
+// where R_t >= max |a'| over the tile's rows and (z_q, w_q) come from K2p (ia_gather.h):
 // z_q >= U'_q - |q'|^2 + (rounding terms), w_q >= 2^-8 |q'|.  The hi-only value misses
 // sum(hi_a lo_q + lo_a hi_q + lo_a lo_q) and carries its fp32 accumulation error, together
 // < 2^-10 (|a'|^2 + 2|a'||q'|) + 2^-24 (16|a'| + 16|q'| + 300) (f16 rounding 2^-11 relative,

@@ -1,5 +1,5 @@
 // ia_prune.h — device helpers of the certified pruned distance scan, shared by
-// the per-level setup (ia_prune.hip), the query gather K2p (ia_kernels.hip) and the pruned
+// the per-level setup (ia_prune.hip), the query gather K2p (ia_gather.h) and the pruned
 // MFMA scan K3p (ia_k3h.hip).
 //
 // Bound: for orthonormal u_1..u_k and a DB row a, sum_i (u_i . (a - q))^2 <= |a - q|^2, and

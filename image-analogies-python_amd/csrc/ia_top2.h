@@ -1,4 +1,4 @@
-// ia_top2.h — device types shared by the MFMA distance kernels (ia_kernels.hip, ia_k3h.hip):
+// ia_top2.h — device types shared by the MFMA distance kernels (ia_k3.hip, ia_k3h.hip):
 // MFMA operand/accumulator vectors and the per-subset top-2 record with its merge.
 #pragma once
 #include <hip/hip_runtime.h>

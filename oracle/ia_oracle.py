@@ -145,7 +145,7 @@ def blas_ddot_sq(x):
     """x.dot(x) in the order of the BLAS behind numpy on the host that made the golden vectors
     (OpenBLAS 0.3.29 ddot, SkylakeX kernel; matched bit-for-bit against np.dot for n = 1..165).
     np.linalg.norm(v, ord=2) of a 1-D v is sqrt(v.dot(v)), so compute_distance's last bits
-    depend on this order; the GPU's blas_dot_sq (ia_kernels.hip) restates it.  Pure Python,
+    depend on this order; the GPU's blas_dot_sq (ia_dev.h) restates it.  Pure Python,
     exact FMA via fractions: test-sized inputs only."""
     x = [float(v) for v in x]
     n = len(x)

@@ -5,7 +5,7 @@ every best_approximate_match index ('app_ix'), every best_coherence_match return
 
 NN indices, coherence picks and distances must be bit-exact.  compute_distance =
 norm((a - q) * w)**2: numpy's norm of a 1-D vector is sqrt(x.dot(x)), a BLAS ddot whose summation
-order the kernels restate (blas_dot_sq in ia_kernels.hip; oracle blas_ddot_sq, pinned against
+order the kernels restate (blas_dot_sq in ia_dev.h; oracle blas_ddot_sq, pinned against
 these vectors in tests/test_oracle_golden.py), and `** 2` on the numpy scalar is libm pow, which
 the host applies to the kernel's dot (_native.Context.synthesize_level).
 """

@@ -1,5 +1,5 @@
 """The scan and merge options no other test sets (include/ia.h ia_set_option), pinned to the
-reference's recorded runs: "early_gather" (gather_p_early, ia_kernels.hip: a second copy of the
+reference's recorded runs: "early_gather" (gather_p_early, ia_gather.h: a second copy of the
 query gather with its own summation orders and a U' without the row above's candidates),
 "rec_wt" (write-through record stores of the pruned scan, ia_k3h.hip), "prefetch_next" (without
 it early_gather does not apply) and "stamps" (every pruned-scan and merge workgroup stores its

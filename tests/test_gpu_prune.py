@@ -195,7 +195,7 @@ def test_pruned_scan_over_512_tiles_per_workgroup(ctx, variant):
 @pytest.mark.parametrize('name', ['g64', 'ties128', 'k25', 'g256'])
 def test_fused_sort_matches_reference(ctx, name, opt):
     """option fuse_sort with every level pruned: each fused merge + gather ranks the next step's
-    keys across its waves and writes the presorted scan inputs (ia_kernels.hip sorted_publish);
+    keys across its waves and writes the presorted scan inputs (ia_gather.h sorted_publish);
     s, im and B' of every level equal the reference run's."""
     from ia_amd import _native
     from golden_util import BIG_CASES, E2E_CASES, load_e2e

@@ -95,7 +95,7 @@ def test_blas_dot_order_three_channel():
 def test_libm_pow_square_differs_from_product_only_near_midpoints():
     """compute_distance ends in `norm(...) ** 2` on a numpy scalar = libm pow(y, 2.0), which is
     not always the correctly rounded y * y the kernels use.  K4's audit (pow2_alt in
-    ia_kernels.hip, ia_stats.kappa_ambiguous) assumes every difference lies where the exact
+    ia_dev.h, ia_stats.kappa_ambiguous) assumes every difference lies where the exact
     square is within 0.9 half-ulp of a rounding midpoint and equals the neighbour toward it:
     checked here against this host's libm on random y."""
     import math
