@@ -172,8 +172,11 @@ __device__ __forceinline__ void merge_fused(const LevelGeo &g, const StepDesc &s
     row_dists<CH>(a.db64, my_row, qs, ws, unw, wsq);
   }
   // bound audit: the exact distance of every reranked candidate must lie within eps of its
-  // MFMA value + |q'|^2 (a violation would void the certification; counted, never expected)
-  const bool viol = lane >= NCOH && my_row >= 0 && fabs(unw - qn2 - (double)my_v) > eps;
+  // MFMA value + |q'|^2 (a violation would void the certification; counted, never expected).
+  // unw and qn2 are fp64 sums in different orders: their own roundings, <= (D + 3) 2^-53 of each
+  // and the counterpart of cert_theta's 1e-13 term, matter once eps is 0 (a constant A side under
+  // the fp32 matcher: R = 0, every MFMA value 0, unw and qn2 equal up to their last bits)
+  const bool viol = lane >= NCOH && my_row >= 0 && fabs(unw - qn2 - (double)my_v) > eps + 1e-13 * (unw + qn2);
   const bool any_viol = __ballot(viol) != 0;
 #if IA_PROBE & 8
   if (unw == 12345.) stamp[7] = 2;
