@@ -121,7 +121,9 @@ typedef struct {
  * Bp: in = initial B' level (initialize_Bp, img_preprocess.py:66-78), out = synthesised.
  * s_out (N x 2, row/col in A) and im_out (N) are the reference's s / im lists for this level. */
 typedef struct {
-  int ch;          /* channels per pixel: 1 (luminance / grayscale) or 3 */
+  int ch;          /* channels per pixel: 1 (luminance / grayscale), 2 or 3.  The reference writes
+                    * colour back for 3 channels only, so 2 channels have no reference run: they
+                    * are pinned to the oracle (oracle/ia_oracle.py, tests/test_gpu_channels.py) */
   int n_ap;        /* number of A' images (Ap_fname_list) */
   int a_h, a_w;    /* A level l */
   int b_h, b_w;    /* B level l */

@@ -70,12 +70,19 @@ def check_debug_records(z, out, Bp, st, name='', kappa_equalities=False):
 PRUNE_MIN_ROWS_DEFAULT = 1 << 19
 
 
-def scan_counts(z, J, qtmax=11):
+# query tiles one scan launch takes (a wider step runs in blocks), by matcher and channel count:
+# the split-f16 scan's ia_k3h_qtmax(KS) with KS = ia_ks_for(ch) = 4 / 7, the fp32 scan's
+# ia_k3_qtmax(KH) with KH = 28 / 56 / 84 (image-analogies-python_amd/csrc/ia_k3.hip).  3 channels
+# have no split-f16 instance (ia_ks_for(3) = 0): either matcher setting runs the fp32 scan.
+QTMAX = {('f16x3', 1): 11, ('f16x3', 2): 8, ('f16x3', 3): 3, ('f32', 1): 11, ('f32', 2): 5, ('f32', 3): 3}
+
+
+def scan_counts(z, J, matcher='f16x3'):
     """What the scan launch counters of one run over every level of fixture z with J batched jobs
     must add up to, per level: n = DB tiles of 32 rows, steps = the wavefront steps that hold a
-    query, qtt / nqb = their query tiles and query blocks (qtmax tiles per block: 11 is the
-    1-channel split-f16 scan's, ia_k3h_qtmax) summed over those steps.  Every scan path visits each
-    (DB tile, query tile) pair and each (DB tile, query block) once per step, so
+    query, qtt / nqb = their query tiles and query blocks (QTMAX tiles per block, for the scan the
+    matcher - 'f16x3' or 'f32' - and z's channel count select) summed over those steps.  Every scan
+    path visits each (DB tile, query tile) pair and each (DB tile, query block) once per step, so
     dist_pairs_full = sum n qtt and dist_tiles_full = sum n nqb whatever kernel runs; only the
     launch count tells the paths apart (one per block, or one per step and shard)."""
     from ia_amd import _native
@@ -83,7 +90,7 @@ def scan_counts(z, J, qtmax=11):
     for level in range(1, z['L']):
         a_h, a_w = z['A_pyr'][level].shape[:2]
         h, w = z['B_pyr'][level].shape[:2]
-        assert z['A_pyr'][level].ndim == 2 or z['A_pyr'][level].shape[2] == 1   # qtmax = 11
+        qtmax = QTMAX[matcher, 1 if z['A_pyr'][level].ndim == 2 else z['A_pyr'][level].shape[2]]
         T, _ = _native.wavefront_shape(h, w)
         M = [m for m in (_native.wavefront_step(h, w, t)[1] for t in range(T)) if m > 0]
         qtt = [-(-J * m // 32) for m in M]
