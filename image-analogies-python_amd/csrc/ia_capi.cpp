@@ -198,6 +198,8 @@ struct ia_index {
   ia_ctx *ctx = nullptr;
   int64_t n = 0;
   int d = 0, KH = 0, n_tiles = 0, tpw = 0, nwg = 0;
+  double sc = 1.;             // power-of-two prescale of the centred fp32 copy (ia_dense.hip)
+  std::vector<double> mu_h;   // column means (the queries' range check)
   DevBuf pts, db, mu, Rbits, q, q64, qn2, qf, rec, recT, idx, dist, counters;
   DevBuf cpx, cs, cim, cout;  // ia_coherence_batch staging
 };
@@ -2238,6 +2240,22 @@ int ia_index_build(ia_ctx *c, const double *pts, int64_t n, int d, ia_index **ou
   for (int64_t i = 0; i < n; i++)
     for (int f = 0; f < d; f++) mu[f] += pts[i * d + f];
   for (int f = 0; f < d; f++) mu[f] /= (double)n;
+  // prescale: 2^-e with the largest centred |value| in [2^(e-1), 2^e), so the fp32 scan sees values
+  // in [0.5, 1) (|e| <= 500 keeps sc^2 a normal fp64; an all-equal DB keeps sc = 1)
+  double amax = 0.;
+  for (int64_t i = 0; i < n; i++)
+    for (int f = 0; f < d; f++) amax = std::fmax(amax, std::fabs(pts[i * d + f] - mu[f]));
+  if (!std::isfinite(amax)) {  // (fmax drops a NaN: the means carry it)
+    delete x;
+    return fail(IA_EINVAL, "ia_index_build: rows must be finite (and their column sums too)");
+  }
+  for (int f = 0; f < d; f++)
+    if (!std::isfinite(mu[f])) {
+      delete x;
+      return fail(IA_EINVAL, "ia_index_build: rows must be finite (and their column sums too)");
+    }
+  x->sc = amax > 0. ? std::ldexp(1.0, -std::max(-500, std::min(500, std::ilogb(amax) + 1))) : 1.;
+  x->mu_h = mu;
   int rc;
   if ((rc = x->pts.ensure((size_t)n * d * 8)) || (rc = x->db.ensure((size_t)x->n_tiles * IA_TILE * 2 * KH * 4)) ||
       (rc = x->mu.ensure((size_t)d * 8)) || (rc = x->Rbits.ensure(4)) || (rc = x->counters.ensure(32))) {
@@ -2247,7 +2265,7 @@ int ia_index_build(ia_ctx *c, const double *pts, int64_t n, int d, ia_index **ou
   hipMemcpyAsync(x->pts.p, pts, (size_t)n * d * 8, hipMemcpyHostToDevice, c->st);
   hipMemcpyAsync(x->mu.p, mu.data(), (size_t)d * 8, hipMemcpyHostToDevice, c->st);
   hipMemsetAsync(x->Rbits.p, 0, 4, c->st);
-  ia_launch_dense_db(KH, x->pts.as<double>(), n, d, x->n_tiles, x->mu.as<double>(), x->db.as<float4>(),
+  ia_launch_dense_db(KH, x->pts.as<double>(), n, d, x->n_tiles, x->mu.as<double>(), x->sc, x->db.as<float4>(),
                      x->Rbits.as<unsigned>(), c->st);
   hipError_t e = hipStreamSynchronize(c->st);
   if (e == hipSuccess) e = hipGetLastError();
@@ -2263,6 +2281,13 @@ int ia_index_query(ia_index *x, const double *q, int64_t nq, int64_t *idx_out, d
   if (!x || !q || !idx_out || nq < 0) return fail(IA_EINVAL, "ia_index_query: bad arguments");
   if (nq == 0) return IA_OK;
   ia_ctx *c = x->ctx;
+  // the prescaled fp32 copy of a query must stay far inside fp32: refuse queries farther than 2^100
+  // times the rows' spread from their mean (the rows themselves are <= 1 there), and NaN / inf
+  for (int64_t i = 0; i < nq; i++)
+    for (int f = 0; f < x->d; f++)
+      if (!(std::fabs((q[i * x->d + f] - x->mu_h[f]) * x->sc) <= 0x1p100))
+        return fail(IA_EINVAL, "ia_index_query: query " + std::to_string(i) +
+                                   " is not finite or farther than 2^100 x the rows' spread from their mean");
   HIP_TRY(hipSetDevice(c->dev));
   const int64_t BATCH = 4096;
   const int64_t bmax = std::min(nq, BATCH), bpad = (bmax + IA_TILE - 1) / IA_TILE * IA_TILE;
@@ -2300,7 +2325,7 @@ int ia_index_query(ia_index *x, const double *q, int64_t nq, int64_t *idx_out, d
     const int64_t nb = std::min(BATCH, nq - b0);
     const int Mpad = (int)((nb + IA_TILE - 1) / IA_TILE * IA_TILE);
     HIP_TRY(hipMemcpyAsync(x->q.p, q + b0 * x->d, (size_t)nb * x->d * 8, hipMemcpyHostToDevice, c->st));
-    ia_launch_dense_query(x->KH, x->q.as<double>(), nb, x->d, Mpad, x->mu.as<double>(), x->qn2.as<double>(),
+    ia_launch_dense_query(x->KH, x->q.as<double>(), nb, x->d, Mpad, x->mu.as<double>(), x->sc, x->qn2.as<double>(),
                           x->qf.as<float>(), c->st);
     const int qtt = Mpad / IA_TILE;
     for (int qt0 = 0; qt0 < qtt; qt0 += qtmax) {
@@ -2308,7 +2333,7 @@ int ia_index_query(ia_index *x, const double *q, int64_t nq, int64_t *idx_out, d
       ia_launch_k3(x->KH, qt, x->db.as<float4>(), x->qf.as<float4>(), x->n_tiles, x->tpw, qt0, (int)nb, x->nwg, 0, x->n_tiles,
                    x->rec.as<float4>(), x->recT.as<float>(), c->st);
     }
-    ia_launch_merge_dense(ma, x->pts.as<double>(), x->d, x->q.as<double>(), nb, x->idx.as<int64_t>(),
+    ia_launch_merge_dense(ma, x->pts.as<double>(), x->d, x->q.as<double>(), nb, x->sc * x->sc, x->idx.as<int64_t>(),
                           x->dist.as<double>(), c->st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(idx_out + b0, x->idx.p, (size_t)nb * 8, hipMemcpyDeviceToHost, c->st));

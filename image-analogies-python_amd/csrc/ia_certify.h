@@ -5,9 +5,10 @@
 #include "ia_dev.h"
 
 // the certified single-rank winner of query m (exact NN over this rank's shard); RPL records per
-// lane (nwg <= 64 RPL)
+// lane (nwg <= 64 RPL).  dsc: dist() * dsc is in the units of the scan's values (the prescaled
+// index, ia_capi.cpp ia_index_build; 1 on the level path)
 template <int RPL = IA_WG_TARGET / IA_WAVE, class DistFn>
-__device__ Winner certified_winner(const MergeArgs &a, int m, DistFn &&dist, unsigned *stat_out) {
+__device__ Winner certified_winner(const MergeArgs &a, int m, DistFn &&dist, unsigned *stat_out, double dsc = 1.0) {
   const int lane = threadIdx.x & 63;
   const float4 *rr = a.rec + (int64_t)m * a.nwg;
   const float *rT = a.recT + (int64_t)m * a.nwg;
@@ -65,7 +66,7 @@ __device__ Winner certified_winner(const MergeArgs &a, int m, DistFn &&dist, uns
 
   // certification: every unlisted row of chunk w has MFMA value >= T_w, hence true distance
   // >= T_w + |q'|^2 - eps.  Chunks with T_w <= theta may hide a row that beats or ties bd.
-  const double theta = cert_theta(a, R, qn, qn2, bd);
+  const double theta = cert_theta(a, R, qn, qn2, bd * dsc);
   const float thetaf = round_down_f(theta);  // (t <= theta  <=>  t <= theta rounded down, t a float)
   unsigned long long nfb = 0;
 #pragma unroll

@@ -80,11 +80,18 @@ __global__ void __launch_bounds__(IA_WG) k_reduce_stats(const unsigned *__restri
 
 // ------------------------------------------------------------------------------------------
 // dense (FLANN-compatible index) variants: rows given as n x d fp64
+//
+// The fp32 copy of the rows and of the queries is centred (mu) and multiplied by sc, a power of two
+// chosen at ia_index_build so that the largest centred |value| lies in [0.5, 1): the scan's squares
+// and products then neither overflow nor underflow fp32 whatever the caller's units, which is
+// what the error bound ia_eps_c assumes (there is no range gate as on the level path).  The scan's
+// values, qn2 and R are in the scaled units; the exact distances are computed from the caller's
+// rows and enter the certification threshold multiplied by dsc = sc^2 (exact).
 // ------------------------------------------------------------------------------------------
 template <int KH>
 __global__ void __launch_bounds__(IA_WG) k_dense_db_build(const double *__restrict__ pts, int64_t n, int d, int n_tiles,
-                                                           const double *__restrict__ mu, float4 *__restrict__ db,
-                                                           unsigned *__restrict__ Rbits) {
+                                                           const double *__restrict__ mu, double sc,
+                                                           float4 *__restrict__ db, unsigned *__restrict__ Rbits) {
   constexpr int KP = KH / 4;
   const int64_t pos = (int64_t)blockIdx.x * IA_WG + threadIdx.x;
   if (pos >= (int64_t)n_tiles * IA_TILE) return;
@@ -100,7 +107,7 @@ __global__ void __launch_bounds__(IA_WG) k_dense_db_build(const double *__restri
       for (int e = 0; e < 4; e++) {
         const int f = h * KH + 4 * p + e;
         if (f < d) {
-          double a = real ? pts[row * d + f] - mu[f] : 0.;
+          double a = real ? (pts[row * d + f] - mu[f]) * sc : 0.;
           norm += a * a;
           v[e] = (float)a;
         } else if (f == d) {
@@ -117,8 +124,8 @@ __global__ void __launch_bounds__(IA_WG) k_dense_db_build(const double *__restri
 
 template <int KH>
 __global__ void __launch_bounds__(IA_WG) k_dense_query(const double *__restrict__ q, int64_t nq, int d, int Mpad,
-                                                        const double *__restrict__ mu, double *__restrict__ qn2,
-                                                        float *__restrict__ qf) {
+                                                        const double *__restrict__ mu, double sc,
+                                                        double *__restrict__ qn2, float *__restrict__ qf) {
   constexpr int KP = KH / 4;
   const int lane = threadIdx.x & 63;
   const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
@@ -127,7 +134,7 @@ __global__ void __launch_bounds__(IA_WG) k_dense_query(const double *__restrict_
   for (int f = lane; f < 2 * KH; f += IA_WAVE) {
     float v = 0.f;
     if (m < nq && f < d) {
-      const double qc = q[(int64_t)m * d + f] - mu[f];
+      const double qc = (q[(int64_t)m * d + f] - mu[f]) * sc;
       ss += qc * qc;
       v = -2.f * (float)qc;
     } else if (m < nq && f == d) {
@@ -141,7 +148,8 @@ __global__ void __launch_bounds__(IA_WG) k_dense_query(const double *__restrict_
 }
 
 __global__ void __launch_bounds__(IA_WG) k_merge_dense(MergeArgs ma, const double *__restrict__ pts, int d, const double *__restrict__ q,
-                                                        int64_t nq, int64_t *__restrict__ idx_out, double *__restrict__ dist_out) {
+                                                        int64_t nq, double dsc, int64_t *__restrict__ idx_out,
+                                                        double *__restrict__ dist_out) {
   const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
   if (m >= nq) return;
   const double *qm = q + (int64_t)m * d;
@@ -152,7 +160,7 @@ __global__ void __launch_bounds__(IA_WG) k_merge_dense(MergeArgs ma, const doubl
       const double x = a[f] - qm[f];
       return x * x;
     }, d);
-  }, &stat);
+  }, &stat, dsc);
   if ((threadIdx.x & 63) == 0) {
     idx_out[m] = wn.idx;
     dist_out[m] = wn.d;
@@ -246,23 +254,23 @@ void ia_launch_reduce_stats(const unsigned *pstat, int64_t n, unsigned long long
   hipLaunchKernelGGL(k_reduce_stats, dim3((unsigned)nwg), dim3(IA_WG), 0, st, pstat, n, counters);
 }
 
-void ia_launch_dense_db(int KH, const double *pts, int64_t n, int d, int n_tiles, const double *mu, float4 *db,
+void ia_launch_dense_db(int KH, const double *pts, int64_t n, int d, int n_tiles, const double *mu, double sc, float4 *db,
                         unsigned *Rbits, hipStream_t st) {
   dim3 grid(cdiv((int64_t)n_tiles * IA_TILE, IA_WG));
-  if (KH == 28) hipLaunchKernelGGL(k_dense_db_build<28>, grid, dim3(IA_WG), 0, st, pts, n, d, n_tiles, mu, db, Rbits);
-  else if (KH == 56) hipLaunchKernelGGL(k_dense_db_build<56>, grid, dim3(IA_WG), 0, st, pts, n, d, n_tiles, mu, db, Rbits);
-  else hipLaunchKernelGGL(k_dense_db_build<84>, grid, dim3(IA_WG), 0, st, pts, n, d, n_tiles, mu, db, Rbits);
+  if (KH == 28) hipLaunchKernelGGL(k_dense_db_build<28>, grid, dim3(IA_WG), 0, st, pts, n, d, n_tiles, mu, sc, db, Rbits);
+  else if (KH == 56) hipLaunchKernelGGL(k_dense_db_build<56>, grid, dim3(IA_WG), 0, st, pts, n, d, n_tiles, mu, sc, db, Rbits);
+  else hipLaunchKernelGGL(k_dense_db_build<84>, grid, dim3(IA_WG), 0, st, pts, n, d, n_tiles, mu, sc, db, Rbits);
 }
-void ia_launch_dense_query(int KH, const double *q, int64_t nq, int d, int Mpad, const double *mu, double *qn2, float *qf,
-                           hipStream_t st) {
+void ia_launch_dense_query(int KH, const double *q, int64_t nq, int d, int Mpad, const double *mu, double sc, double *qn2,
+                           float *qf, hipStream_t st) {
   dim3 grid(cdiv(Mpad, IA_WG / IA_WAVE));
-  if (KH == 28) hipLaunchKernelGGL(k_dense_query<28>, grid, dim3(IA_WG), 0, st, q, nq, d, Mpad, mu, qn2, qf);
-  else if (KH == 56) hipLaunchKernelGGL(k_dense_query<56>, grid, dim3(IA_WG), 0, st, q, nq, d, Mpad, mu, qn2, qf);
-  else hipLaunchKernelGGL(k_dense_query<84>, grid, dim3(IA_WG), 0, st, q, nq, d, Mpad, mu, qn2, qf);
+  if (KH == 28) hipLaunchKernelGGL(k_dense_query<28>, grid, dim3(IA_WG), 0, st, q, nq, d, Mpad, mu, sc, qn2, qf);
+  else if (KH == 56) hipLaunchKernelGGL(k_dense_query<56>, grid, dim3(IA_WG), 0, st, q, nq, d, Mpad, mu, sc, qn2, qf);
+  else hipLaunchKernelGGL(k_dense_query<84>, grid, dim3(IA_WG), 0, st, q, nq, d, Mpad, mu, sc, qn2, qf);
 }
-void ia_launch_merge_dense(const MergeArgs &ma, const double *pts, int d, const double *q, int64_t nq, int64_t *idx,
-                           double *dist, hipStream_t st) {
-  hipLaunchKernelGGL(k_merge_dense, dim3(cdiv(nq, IA_WG / IA_WAVE)), dim3(IA_WG), 0, st, ma, pts, d, q, nq, idx, dist);
+void ia_launch_merge_dense(const MergeArgs &ma, const double *pts, int d, const double *q, int64_t nq, double dsc,
+                           int64_t *idx, double *dist, hipStream_t st) {
+  hipLaunchKernelGGL(k_merge_dense, dim3(cdiv(nq, IA_WG / IA_WAVE)), dim3(IA_WG), 0, st, ma, pts, d, q, nq, dsc, idx, dist);
 }
 void ia_launch_coherence_batch(const double *pts, int64_t n, int d, const double *q, int64_t nq, const int32_t *px,
                                const int32_t *s, const int32_t *im, int64_t n_s, int a_h, int a_w, int bp_w, int pad,

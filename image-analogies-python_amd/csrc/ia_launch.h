@@ -29,12 +29,12 @@ void ia_launch_reduce_stats(const unsigned *pstat, int64_t n, unsigned long long
 // option "stamps": per launch (min start, max end) ticks over its stride workgroup slots
 void ia_launch_stamp_durations(const unsigned long long *stamps, int n, int stride, unsigned long long *span, hipStream_t st,
                                unsigned long long *span2 = nullptr);
-void ia_launch_dense_db(int KH, const double *pts, int64_t n, int d, int n_tiles, const double *mu, float4 *db,
+void ia_launch_dense_db(int KH, const double *pts, int64_t n, int d, int n_tiles, const double *mu, double sc, float4 *db,
                         unsigned *Rbits, hipStream_t st);
-void ia_launch_dense_query(int KH, const double *q, int64_t nq, int d, int Mpad, const double *mu, double *qn2, float *qf,
-                           hipStream_t st);
-void ia_launch_merge_dense(const MergeArgs &ma, const double *pts, int d, const double *q, int64_t nq, int64_t *idx,
-                           double *dist, hipStream_t st);
+void ia_launch_dense_query(int KH, const double *q, int64_t nq, int d, int Mpad, const double *mu, double sc, double *qn2,
+                           float *qf, hipStream_t st);
+void ia_launch_merge_dense(const MergeArgs &ma, const double *pts, int d, const double *q, int64_t nq, double dsc,
+                           int64_t *idx, double *dist, hipStream_t st);
 void ia_launch_coherence_batch(const double *pts, int64_t n, int d, const double *q, int64_t nq, const int32_t *px,
                                const int32_t *s, const int32_t *im, int64_t n_s, int a_h, int a_w, int bp_w, int pad,
                                int32_t *p_out, int32_t *img_out, int32_t *r_out, unsigned *err, hipStream_t st);

@@ -282,10 +282,14 @@ int ia_pipeline_depend(ia_ctx *ctx, ia_ctx *prev, int prev_gen);
 int ia_pipeline_generation(ia_ctx *ctx);
 
 /* ---- FLANN-compatible exact index (algorithms.py:56,69,74) -------------------------------- */
-/* build_index(pts): pts is n x d fp64 (row-major), d <= 167. */
+/* build_index(pts): pts is n x d fp64 (row-major), d <= 167, every value and every column sum
+ * finite (IA_EINVAL otherwise).  Any units: the fp32 scan works on a centred copy prescaled by a
+ * power of two chosen from the rows, so the answers below are exact at 2^-80 as at 2^+70. */
 int ia_index_build(ia_ctx *ctx, const double *pts, int64_t n, int d, ia_index **out);
 /* nn_index(q, 1): exact 1-NN, squared L2 in fp64 with numpy's pairwise summation order,
- * lowest index on ties.  q is nq x d fp64; idx_out (nq) int64, dist_out (nq) fp64 (may be NULL). */
+ * lowest index on ties.  q is nq x d fp64; idx_out (nq) int64, dist_out (nq) fp64 (may be NULL).
+ * IA_EINVAL (nothing written) when a query value is not finite or lies farther from its column's
+ * mean than 2^100 times the largest such distance of any row value. */
 int ia_index_query(ia_index *index, const double *q, int64_t nq, int64_t *idx_out, double *dist_out);
 void ia_index_destroy(ia_index *index);
 /* best_coherence_match (algorithms.py:92-130) for nq B' pixels against the index's rows (the

@@ -15,6 +15,10 @@ pytestmark = pytest.mark.gpu
 
 
 def test_gpu_pyramid_matches_host_and_skimage(ctx):
+    """The tiny shapes (2, 7), (5, 1), (1, 1) run no reduction through compute_gaussian_pyramid(img, 3)
+    (their side is already <= min_size), so they are also reduced through ia_gaussian_pyramid directly,
+    1 to 3 times, against _pyramid_reduce applied as often (tests/test_gpu_api_edges.py
+    test_pyramid_small_sides has the full list of small shapes)."""
     import ia_amd  # noqa: F401
     from ia_amd import img_preprocess as ip
     g = np.load(os.path.join(GOLDEN, 'pyramids.npz'))
@@ -35,6 +39,12 @@ def test_gpu_pyramid_matches_host_and_skimage(ctx):
             host = ip.compute_gaussian_pyramid(img, 3, n)
             gpu = ip.compute_gaussian_pyramid(img, 3, n, ctx=ctx)
             assert len(gpu) == len(host) and all(np.array_equal(a, b) for a, b in zip(gpu, host)), shp
+        if min(shp[:2]) <= 3:
+            for n in (1, 2, 3):
+                gpu, ref = ctx.gaussian_pyramid(img, n, ip.gaussian_weights()), []
+                for _ in range(n):
+                    ref.append(ip._pyramid_reduce(ref[-1] if ref else img))
+                assert len(gpu) == n and all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(gpu, ref)), shp
 
 
 def test_gpu_color_matrix_matches_reference(ctx):
