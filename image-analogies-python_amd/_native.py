@@ -116,6 +116,7 @@ EXPORTS = {
     'ia_merge_winners': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                         ctypes.c_void_p, ctypes.c_void_p]),
     'ia_chain_budget': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'ia_chain_choice': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'ia_wavefront_shape': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                           ctypes.POINTER(ctypes.c_int64)]),
     'ia_wavefront_step': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int),
@@ -475,6 +476,11 @@ def shard_rows(n_rows, world, rank):
 def chain_budget(n_cu, vgprs, api_blocks_per_cu, wg_threads=64):
     """include/ia.h ia_chain_budget: deadlock-free handoff-chained waves in flight (0: never chain)"""
     return lib().ia_chain_budget(n_cu, vgprs, api_blocks_per_cu, wg_threads)
+
+
+def chain_choice(level_waves, in_flight, budget, two_wave=1):
+    """include/ia.h ia_chain_choice: 2 (two-wave workgroups, twice the waves reserved), 1 (one-wave) or 0 (unchained)"""
+    return lib().ia_chain_choice(level_waves, in_flight, budget, two_wave)
 
 
 def wavefront_shape(h, w):

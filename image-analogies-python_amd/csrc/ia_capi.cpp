@@ -38,6 +38,12 @@ thread_local std::string g_last_error;
 // synchronous: its launches are done when it returns); otherwise it runs the separate gather /
 // merge launches.  (cfg5's 16-job batches of 512^2 steps, 2,736 waves per launch on three
 // streams, hit the 20 s handoff timeout without this.)
+// Two-wave workgroups (option "gather_wave"): a workgroup is dispatched whole, so a gather wave's
+// own merge wave is always resident beside it; a gather wave waits only for that merge wave (one
+// workgroup barrier) and for the slot of the row above, published by the MERGE wave of a
+// workgroup with a lower index, dispatched before it; merge waves wait for nothing, so they
+// always finish, release their gather waves, and the waits drain in index order as before.  Such
+// a level holds two resident slots per query and reserves twice its waves (ia_chain_choice).
 static std::atomic<int> g_chain_waves{0};
 struct ChainReservation {
   int n = 0;
@@ -144,6 +150,7 @@ struct ia_ctx {
   int hand_rows = 0;
   int prefetch_next = 1;         // option "prefetch_next" (NextStep::prefetch)
   int early_gather = 1;          // option "early_gather" (NextStep::early)
+  int gather_wave = 1;           // option "gather_wave" (NextStep::gwave): the early path on two-wave workgroups
   int nn_bound = 1;              // option "nn_bound" (JobPtrs::nn): the pruned one-rank levels' gathers also
                                  // bound U' by the causal neighbours' exact NN rows, shifted
   int fuse_sort = 0;             // option "fuse_sort": the fused gathers of step t + 1 also sort it (NextStep::kslot);
@@ -475,6 +482,11 @@ int ia_set_option(ia_ctx *c, const char *name, int value) {
     c->early_gather = value;
     return IA_OK;
   }
+  if (!std::strcmp(name, "gather_wave")) {
+    if (value != 0 && value != 1) return fail(IA_EINVAL, "ia_set_option: gather_wave must be 0 or 1");
+    c->gather_wave = value;
+    return IA_OK;
+  }
   if (!std::strcmp(name, "prefetch_next")) {
     if (value != 0 && value != 1) return fail(IA_EINVAL, "ia_set_option: prefetch_next must be 0 or 1");
     c->prefetch_next = value;
@@ -675,6 +687,16 @@ int ia_chain_budget(int n_cu, int vgprs, int api_blocks_per_cu, int wg_threads) 
   if (per_cu <= 0) return 0;
   const int slots = per_cu * n_cu;
   return 2 * slots - (2 * slots) / 16;
+}
+int ia_chain_choice(int level_waves, int in_flight, int budget, int two_wave) {
+  // what a level whose widest chained launch has level_waves one-wave workgroups takes of the
+  // budget, in_flight of it reserved already: the two-wave form (option "gather_wave") reserves
+  // twice its waves; refused that, the one-wave form its single reservation; refused that too,
+  // the level runs unchained
+  if (level_waves <= 0 || in_flight < 0 || budget <= 0) return 0;
+  const int64_t left = (int64_t)budget - in_flight;
+  if (two_wave && 2 * (int64_t)level_waves <= left) return 2;
+  return level_waves <= left ? 1 : 0;
 }
 int ia_wavefront_shape(int h, int w, int64_t *steps, int64_t *max_queries) {
   if (h < 1 || w < 1) return fail(IA_EINVAL, "ia_wavefront_shape: empty level");
@@ -1327,6 +1349,7 @@ struct LevelRun {
   std::vector<int64_t> shard_rows;  // real DB rows in each shard (unpruned flops)
   bool chain = false;               // fused K4(t) + K2(t + 1) launches, handoff-chained (option "fuse_gather")
   ChainReservation &chain_res;
+  bool gwave = false;               // ... as two-wave workgroups, reserved as such (option "gather_wave")
   bool fsort = false;               // their gathers may also sort the next step (option "fuse_sort")
   int64_t gathered = -1;            // the step whose gather the previous fused launch ran
   bool gsort = false;               // ... and that launch also sorted it (no K2s, no in-scan sort)
@@ -1402,7 +1425,18 @@ struct LevelRun {
     const int J = P.J;
     chain = c->fuse_gather && P.use_h && g.ch == 1 && g.bw >= 3 && (P.prune || c->fuse_unpruned) &&
             ((!P.multi && !P.xo && mas[0].nwg <= 4 * IA_WAVE) || (P.xo && P.prune));
-    if (chain && !chain_res.take((int)(P.Mpad_max + J) + (P.xo ? 1 : 0), c->chain_budget)) chain = false;
+    // (option "gather_wave": the early path of a one-job, one-rank pruned level whose gathers do
+    // not sort runs two waves per query and reserves them; ia_chain_choice)
+    const bool want_sort = P.prune && !P.xo && (c->fuse_sort == 1 || (c->fuse_sort == 2 && P.Mtmax >= IA_FUSE_SORT_MINQ));
+    const bool two = c->gather_wave && c->early_gather && c->prefetch_next && P.prune && !P.multi && !P.xo && J == 1 && !want_sort;
+    if (chain) {
+      const int lw = (int)(P.Mpad_max + J) + (P.xo ? 1 : 0);
+      // (another thread's level may take budget between the choice and the reservation: then the next smaller form)
+      int form = ia_chain_choice(lw, g_chain_waves.load(), c->chain_budget, two);
+      while (form && !chain_res.take(form * lw, c->chain_budget)) form--;
+      chain = form > 0;
+      gwave = form == 2;
+    }
     if (chain) {
       int rc;  // handoff slots per row of every job (local owner); key slots of the gathers' sort
       if ((rc = grow_uncached(c, (void **)&c->hand, &c->hand_rows, g.bh * J, sizeof(HandSlot))) ||
@@ -1412,8 +1446,7 @@ struct LevelRun {
     }
     // (the gathers' sort waits for every wave of its launch: only while all chained waves in flight
     // fit the resident slots, half the budget)
-    fsort = chain && P.prune && !P.xo && (c->fuse_sort == 1 || (c->fuse_sort == 2 && P.Mtmax >= IA_FUSE_SORT_MINQ)) &&
-            g_chain_waves.load() <= c->chain_budget / 2;
+    fsort = chain && want_sort && g_chain_waves.load() <= c->chain_budget / 2;
     const int64_t n_timed = P.stride ? (P.T + P.stride - 1) / P.stride : 0;
     for (auto *v : {&c->evs, &c->evg, &c->evm})
       if ((int64_t)v->size() < 2 * n_timed) {
@@ -1459,6 +1492,7 @@ struct LevelRun {
     nx.timeout_ticks = IA_WAIT_TICKS;
     nx.prefetch = c->prefetch_next;
     nx.early = c->early_gather;
+    nx.gwave = gwave;
     return nx;
   }
 

@@ -506,3 +506,253 @@ __device__ __forceinline__ void gather_p_early(const LevelGeo &g, const NextStep
 #endif
 #undef IA_GST2
 }
+
+// The gather wave of a two-wave merge + gather workgroup (option "gather_wave", ia_kernels.hip
+// merge_gather_pair): gather_p_early's work split at the merge wave's result instead of behind it.
+// The query's window holds TWO late pixels here: the workgroup's own (r, c - 1), merged by wave 0
+// while this wave runs, and the row above's (r - 1, c + 2); under reflection each can fill several
+// of the twelve B' slots.  gather_wave_pre runs from wave start and needs neither: the constants
+// and prefetched inputs, the candidate rows of every causal neighbour but those two pixels, and
+// all sums (q64, fragments, projections, |q'|^2, the U' partial distances) over the non-late
+// features.  gather_wave_next, still beside the merge, loads the raster successors of the rows
+// the merge wave holds.  gather_wave_post takes the own result: its two candidate rows (shifted
+// source and shifted NN row) from those successors by lane, the own late slots, then the row
+// above's handoff and late slots, and the pruning record.  U' runs over the same candidate rows as
+// gather_p_early's; only the summation order of the own pixel's terms differs (added in slot order
+// after the pairwise / butterfly sums instead of inside them), which the bounds' margins cover.
+struct GatherWave {
+  QConst qk;
+  bool late0 = false, late1 = false;   // this lane's feature is a slot of the own / the row above's pixel
+  bool own = false;                    // this lane's U' candidate comes from the own pixel
+  unsigned long long lm0 = 0, lm1 = 0; // the two pixels' slots (features 43..54), wave-uniform
+  int crow = -1;
+  double qc = 0., ss = 0., p[IA_NPC] = {0., 0., 0., 0.};
+  double part = 0., al[12] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
+  // gather_wave_next: the same of row2, the raster successor of the merge wave's row of this lane
+  int row2 = -1;
+  double part2 = 0., al2[12] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
+#if IA_PROBE & 8
+  unsigned long long t0 = 0, t1 = 0, t2 = 0;
+#endif
+};
+// the U' partial distance of this lane's candidate row over the non-late features and the row's
+// values at the twelve B' slots
+__device__ __forceinline__ void gather_wave_row(const double *__restrict__ db64, int crow, const double *qsh,
+                                                unsigned long long lm, double &part, double *al) {
+  constexpr int D = 55, DS = Geo<1>::DS;
+  double2 rowv[DS / 2];
+  const double2 *src = reinterpret_cast<const double2 *>(db64 + (int64_t)(crow >= 0 ? crow : 0) * DS);
+#pragma unroll
+  for (int i = 0; i < DS / 2; i++) rowv[i] = src[i];
+  const double *rv = reinterpret_cast<const double *>(rowv);
+  part = pw_sum<D>([&](int f) {
+    const double d = rv[f] - qsh[f];
+    return ((lm >> f) & 1ull) ? 0. : d * d;
+  });
+#pragma unroll
+  for (int k = 0; k < 12; k++) al[k] = rv[43 + k];
+}
+template <int KS>
+__device__ __forceinline__ GatherWave gather_wave_pre(const LevelGeo &g, const NextStep &nx, const Imgs &B, const JobPtrs &jp,
+                                                      int mn, int lane, const double *__restrict__ db64, double *qsh) {
+  constexpr int D = 55, KD = 16 * KS;
+  static_assert(KD <= IA_WAVE, "one feature per lane");
+  GatherWave w;
+#if IA_PROBE & 8
+  w.t0 = __builtin_amdgcn_s_memtime();
+#endif
+  w.qk = qconst_load(nx, lane);
+  const QPre pf = qpre_load(g, nx.sn, B, jp, mn, lane);
+  const QPix pn = ia_qpix(nx.sn, g.bw, mn);
+  const int r = pn.r, c = pn.c, qi = pn.qi;
+  const bool above = r >= 1 && c + 2 < g.bw;
+  const int ar = r - 1, ac = c + 2, orr = r, oc = c - 1;  // the two step-t pixels
+  if (lane >= 43 && lane < D) {
+    const int k = lane - 43, y = ia_reflect(r + k / 5 - 2, B.h), x = ia_reflect(c + k % 5 - 2, B.w);
+    w.late0 = y == orr && x == oc;
+    w.late1 = above && y == ar && x == ac;
+  }
+  w.lm0 = __ballot(w.late0);
+  w.lm1 = __ballot(w.late1);
+  const bool late = w.late0 || w.late1;
+  // ---- U' candidate rows (gather_p_early's lanes); the two late pixels' skipped here
+  const bool nnl = jp.nn && lane >= 15 && lane < 30;
+  if (qi > 0 && (lane < 15 || nnl)) {
+    const int k = lane < 15 ? lane : lane - 15;
+    const int nr = r - 2 + k / 5, nc = c - 2 + k % 5;
+    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < qi && !(above && nr == ar && nc == ac)) {
+      if (nr == orr && nc == oc) w.own = true;
+      else w.crow = ucand_row(g, r, c, nr, nc, nnl, pf.sr, pf.sc, pf.si, pf.nn);
+    }
+  }
+  if (lane < D) qsh[lane] = late ? 0. : pf.v;
+  // ---- the non-late features: q64, fragments, projections, |q'|^2 (late lanes hold 0)
+  if (lane < KD) {
+    if (lane < D) {
+      if (!late) {
+        nx.q64[(int64_t)mn * D + lane] = pf.v;
+        w.qc = pf.v - w.qk.mu;
+        w.ss = w.qc * w.qc;
+        put_qh<KS>((_Float16 *)nx.qf, mn, lane, -2.0 * w.qc);
+#pragma unroll
+        for (int i = 0; i < IA_NPC; i++) w.p[i] = w.qk.bas[i] * w.qc;
+      }
+    } else {
+      put_qh<KS>((_Float16 *)nx.qf, mn, lane, lane == D ? IA_NORM_SCALE : 0.);
+    }
+  }
+  w.ss = wave_sum_d_x(w.ss);
+#pragma unroll
+  for (int i = 0; i < IA_NPC; i++) w.p[i] = wave_sum_d_x(w.p[i]);
+  __builtin_amdgcn_wave_barrier();  // qsh written by this wave's lanes, read below
+#if IA_PROBE & 8
+  __builtin_amdgcn_s_waitcnt(0);
+  w.t1 = __builtin_amdgcn_s_memtime();
+#endif
+  gather_wave_row(db64, w.crow, qsh, w.lm0 | w.lm1, w.part, w.al);
+#if IA_PROBE & 8
+  __builtin_amdgcn_s_waitcnt(0);
+  w.t2 = __builtin_amdgcn_s_memtime();
+#endif
+  return w;
+}
+// No dependent row round after the merge: the own pixel's two U' candidates for query (r, c + 1)
+// are `final source + 1` and `NN winner + 1` in A's raster, and both winners are among the rows
+// the merge wave's lanes hold after placement (prow, posted without waiting).  Lane l loads row
+// prow[l] + 1 where that stays inside the image row, and keeps its partial distance and B'-slot
+// values; gather_wave_post picks the two winners' by lane.  The poll is bounded like every wait
+// (err bit 16; then no lane has a row and the post part loads its two rows itself).
+__device__ __forceinline__ void gather_wave_next(const LevelGeo &g, const NextStep &nx, const int *prow, int *prow_on,
+                                                 int lane, const double *__restrict__ db64, const double *qsh,
+                                                 GatherWave &w) {
+  const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
+  bool ok = true;
+  while (__hip_atomic_load(prow_on, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != 1) {
+    if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > nx.timeout_ticks) {
+      atomicOr(nx.err, 16u);
+      ok = false;
+      break;
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+  if (ok) {
+    const int mr = prow[lane];
+    if (mr >= 0 && mr < g.NA && (unsigned)mr % (unsigned)g.aw + 1 < (unsigned)g.aw) w.row2 = mr + 1;
+  }
+  gather_wave_row(db64, w.row2, qsh, w.lm0 | w.lm1, w.part2, w.al2);
+#if IA_PROBE & 8
+  __builtin_amdgcn_s_waitcnt(0);
+  w.t2 = __builtin_amdgcn_s_memtime();
+#endif
+}
+// one late pixel's slots (mask lm, value qc in the slots' lanes), in slot order: its terms of
+// |q'|^2, the projections and this lane's U' distance
+__device__ __forceinline__ void gather_wave_late(GatherWave &w, unsigned long long lm, double v) {
+#pragma unroll
+  for (int k = 0; k < 12; k++) {
+    if ((lm >> (43 + k)) & 1ull) {  // wave-uniform
+      const double qcl = readlane_d(w.qc, 43 + k);
+      w.ss += qcl * qcl;
+#pragma unroll
+      for (int i = 0; i < IA_NPC; i++) w.p[i] += readlane_d(w.qk.bas[i], 43 + k) * qcl;
+      const double d = w.al[k] - v;
+      w.part += d * d;
+    }
+  }
+}
+// h: the own pixel's result (r0, c0, v0, s0r, s0c, i0, n0) from the merge wave
+template <int KS>
+__device__ __forceinline__ void gather_wave_post(const LevelGeo &g, const NextStep &nx, const JobPtrs &jp, int job, int mn,
+                                                 int lane, const double *__restrict__ db64, const double *qsh, const QHand &h,
+                                                 int src_lane, int app_lane, GatherWave &w) {
+  constexpr int D = 55;
+#if IA_PROBE & 8
+  unsigned long long gst[5] = {__builtin_amdgcn_s_memtime(), 0, 0, 0, 0};
+  const bool gprobe = mn == nx.sn.M / 2 && (nx.sn.t % 256) == 129;
+#define IA_GST3(k) do { if (gprobe) { __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); \
+                        gst[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
+#else
+#define IA_GST3(k) do { } while (0)
+#endif
+  const QPix pn = ia_qpix(nx.sn, g.bw, mn);
+  const int r = pn.r, c = pn.c;
+  const bool above = r >= 1 && c + 2 < g.bw;
+  // ---- the own pixel's two candidates: the shifted source (lane 11's) is the successor of the
+  // row the merge wave's lane src_lane held, the shifted NN row (lane 26's) of lane app_lane's:
+  // their partials by lane read (gather_wave_next).  A winner no lane held (an overflow candidate,
+  // a certification rescan; rare) takes the dependent row load.
+  const int from = lane < 15 ? src_lane : app_lane;
+  const int fl = from >= 0 ? from : lane;
+  const int row2 = __shfl(w.row2, fl, 64);
+  const double part2 = __shfl(w.part2, fl, 64);
+  double al2[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) al2[k] = __shfl(w.al2[k], fl, 64);
+  if (w.own) {
+    w.crow = ucand_row(g, r, c, h.r0, h.c0, lane >= 15, h.s0r, h.s0c, h.i0, h.n0);
+    if (from >= 0 && row2 == w.crow) {
+      w.part = part2;
+#pragma unroll
+      for (int k = 0; k < 12; k++) w.al[k] = al2[k];
+    } else {
+      gather_wave_row(db64, w.crow, qsh, w.lm0 | w.lm1, w.part, w.al);
+    }
+  }
+  // ---- its late slots
+  if (w.late0) {
+    nx.q64[(int64_t)mn * D + lane] = h.v0;
+    w.qc = h.v0 - w.qk.mu;
+    put_qh<KS>((_Float16 *)nx.qf, mn, lane, -2.0 * w.qc);
+  }
+  gather_wave_late(w, w.lm0, h.v0);
+  IA_GST3(1);
+  // ---- the row above's result (handoff), then its late slots
+  if (above) {
+    const HandSlot *hs = nx.hand + (int64_t)job * g.bh + (r - 1);
+    const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
+    while (__hip_atomic_load(&hs->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != nx.seq) {
+      if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > nx.timeout_ticks) {
+        atomicOr(nx.err, 16u);
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+    }
+    const double v1 = hs->v;
+    IA_GST3(2);
+    if (w.late1) {
+      nx.q64[(int64_t)mn * D + lane] = v1;
+      w.qc = v1 - w.qk.mu;
+      put_qh<KS>((_Float16 *)nx.qf, mn, lane, -2.0 * w.qc);
+    }
+    gather_wave_late(w, w.lm1, v1);
+  } else {
+    IA_GST3(2);
+  }
+  double u = w.crow >= 0 ? w.part : DBL_MAX;
+  u = wave_min_d_x(u);
+  IA_GST3(3);
+  // ---- the pruning record (gather_p_query's, from these sums)
+  const double ss = w.ss, qn = sqrt(ss);
+  const double(&p)[IA_NPC] = w.p;
+  const bool fin = u < DBL_MAX;
+  const unsigned key = fin ? prune_key(p, w.qk.sc) : IA_PRUNE_KEY_INF;
+  const float up = fin ? round_up_f(u * nx.ufac) : INFINITY;
+  const float z = fin ? round_up_f((double)up - ss + 0x1p-22 * (ss + (double)up) + 0x1p-24 * (16.0 * qn + 300.0)) : INFINITY;
+  const float wd = round_up_f(0x1p-8 * qn * (1.0 + 0x1p-40));
+  if (lane == 0) {
+    nx.qn2[mn] = ss;
+    nx.qinfo[3 * mn] = make_float4(round_down_f(p[0] - IA_PRUNE_MABS), round_down_f(p[1] - IA_PRUNE_MABS),
+                                   round_down_f(p[2] - IA_PRUNE_MABS), round_down_f(p[3] - IA_PRUNE_MABS));
+    nx.qinfo[3 * mn + 1] = make_float4(round_up_f(p[0] + IA_PRUNE_MABS), round_up_f(p[1] + IA_PRUNE_MABS),
+                                       round_up_f(p[2] + IA_PRUNE_MABS), round_up_f(p[3] + IA_PRUNE_MABS));
+    nx.qinfo[3 * mn + 2] = make_float4(up, __uint_as_float(key), z, wd);
+  }
+  IA_GST3(4);
+#if IA_PROBE & 8
+  if (gprobe && lane == 0)
+    printf("WSTAMP bw=%d t=%d M=%d pre=%llu part=%llu wait_merge=%llu own=%llu handoff=%llu late=%llu rec=%llu\n", g.bw,
+           nx.sn.t, nx.sn.M, w.t1 - w.t0, w.t2 - w.t1, gst[0] - w.t2, gst[1] - gst[0], gst[2] - gst[1], gst[3] - gst[2],
+           gst[4] - gst[3]);
+#endif
+#undef IA_GST3
+}

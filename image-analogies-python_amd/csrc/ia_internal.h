@@ -357,6 +357,8 @@ struct NextStep {
   int prefetch;              // option "prefetch_next": the gathers' step-independent inputs load during the merge
   int early;                 // option "early_gather": the merge waves' gathers run everything but the row
                              // above's feature before its handoff (ia_gather.h gather_p_early)
+  int gwave;                 // option "gather_wave", where the level reserved two waves per query: the early
+                             // path as workgroups of a merge wave and a gather wave (k_merge_gather, GW)
   int *sorder;
   float4 *sinfo;
   void *sfrag;

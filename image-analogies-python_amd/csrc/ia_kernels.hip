@@ -17,6 +17,9 @@ struct MergeOut {  // one pixel's result: B' value (first channel), source pixel
   double v;
   int pr, pc, img;
   int nn;  // its certified exact NN row (-1: none)
+  // the lanes whose round-2 row (my_row) is the final source pixel's / the NN winner's (-1: none
+  // holds it: the winner came from an overflow candidate or a certification rescan)
+  int src_lane, app_lane;
 };
 
 // Fused single-rank merge of query m: certified exact NN + coherence + kappa + writeback.
@@ -28,7 +31,7 @@ struct MergeOut {  // one pixel's result: B' value (first channel), source pixel
 // Candidates beyond the 49 rerank lanes (rare) are evaluated by the lanes that listed them.
 // Wave reductions use DPP / permlane exchanges (no LDS round trips).
 struct NoPre {
-  __device__ __forceinline__ void operator()() const {}
+  __device__ __forceinline__ void operator()(int) const {}
 };
 template <int CH, int RPL, class Pre = NoPre>
 __device__ __forceinline__ void merge_fused(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const MergeArgs &a,
@@ -156,8 +159,8 @@ __device__ __forceinline__ void merge_fused(const LevelGeo &g, const StepDesc &s
   const float my_v = lane >= NCOH && my_row >= 0 ? cand_v[lane - NCOH] : FLT_MAX;
   IA_STAMP(2);
   // (k_merge_gather: the next query's step-independent inputs are loaded here, in flight together
-  // with round 2's rows instead of after them)
-  pre();
+  // with round 2's rows instead of after them; the two-wave form posts the lanes' rows here)
+  pre(my_row);
 
   // ---- round 2: one fp64-DB row + its A' value per lane
   double unw = DBL_MAX, wsq = 0.;
@@ -378,6 +381,8 @@ __device__ __forceinline__ void merge_fused(const LevelGeo &g, const StepDesc &s
     out->pc = pc;
     out->img = img;
     out->nn = bi >= 0 && bi < a.NA ? bi : -1;
+    out->src_lane = src_lane;
+    out->app_lane = recompute_app ? -1 : app_lane;
   }
 #if IA_PROBE & 8
   if (lane == 0 && m == sd.M / 2 && (sd.t % 256) == 128) {
@@ -431,18 +436,101 @@ __global__ void __launch_bounds__(IA_PQ_WG) k_merge_level(LevelGeo g, StepDesc s
 // step's pad queries (and, owner-computes ranks with xo_wait, one waiter).  The query buffers
 // alternate by step parity (this launch's merges read step t's half while its gathers write
 // step t + 1's).
+//
+// GW (option "gather_wave"; the one-job, one-rank pruned early path only): workgroups of two waves,
+// one workgroup per wave of the form above.  In a merge workgroup (w < M) wave 0, the merge wave,
+// only merges (r, c) and publishes the row's slot; wave 1, the gather wave, gathers (r, c + 1)
+// from wave start and takes (r, c)'s result from wave 0 through LDS (merge_gather_pair).  The
+// other workgroups (the entering row, the pads) run the one-wave code in wave 0; their wave 1
+// exits at once.
 // ------------------------------------------------------------------------------------------
-template <int RPL, bool PR, bool XO, class JS>
+// A merge workgroup of the two-wave form.  The roles meet at two workgroup barriers, which both
+// reach exactly once each on every path, nothing returning in front of them: one at the start
+// (prow_on cleared), one that hands MergeOut over through LDS: the merge wave reaches it after its
+// merge (it waits for nothing before it), the gather wave after gather_wave_pre / _next, also
+// when it has no query to gather (the row's last column).  The gather wave's two polls - prow_on,
+// set by its own merge wave, which never waits, and the row above's slot after the second barrier
+// - are bounded by nx.timeout_ticks like every handoff wait (err bit 16).
+template <int RPL>
+__device__ __forceinline__ void merge_gather_pair(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const MergeArgs &ma,
+                                                  const JobPtrs &jp, const Imgs &B, const NextStep &nx, int w, int role,
+                                                  int lane, double *qsh, double *wsh, int *crsh, float *cvsh) {
+  constexpr int KS = 4;
+  __shared__ double gq[Geo<1>::DS];  // the gather wave's query row
+  __shared__ MergeOut mo;
+  const QPix px = ia_qpix(sd, g.bw, w);
+  const int mn = px.c + 1 < g.bw ? px.r - nx.sn.r0 : -1;  // the query of step t + 1 (one job)
+  const bool on = mn >= 0 && mn < nx.sn.M;
+  // the merge wave's round-2 rows (my_row of merge_fused), posted as soon as they are placed:
+  // the gather wave loads the raster successor of each (gather_wave_next); prow_on: posted
+  __shared__ int prow[IA_WAVE];
+  __shared__ int prow_on;
+  if (role == 0 && lane == 0) __hip_atomic_store(&prow_on, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __syncthreads();  // (the first of the two barriers: prow_on cleared before anyone polls it)
+  GatherWave gw;
+  MergeOut o;
+  if (role == 0) {
+    auto post = [&](int my_row) {  // no wait: a flag, not a barrier
+      prow[lane] = my_row;
+      __builtin_amdgcn_wave_barrier();
+      if (lane == 0) __hip_atomic_store(&prow_on, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    merge_fused<1, RPL>(g, sd, A, ma, w, jp, px, qsh, wsh, crsh, cvsh, &o, post);
+    if (lane == 0) mo = o;
+  } else if (on) {
+    gw = gather_wave_pre<KS>(g, nx, B, jp, mn, lane, ma.db64, gq);
+    gather_wave_next(g, nx, prow, &prow_on, lane, ma.db64, gq, gw);
+  }
+  __syncthreads();
+  if (role == 0) {
+    // (after the barrier: the gather wave, long there, does not wait for these stores' completion)
+    if (px.r + 1 < g.bh && px.c >= 2) {  // row r + 1 gathers (r + 1, c - 2) at step t + 1
+      HandSlot *hs = nx.hand + px.r;
+      if (lane == 0) {
+        hs->v = o.v;
+        hs->sr = o.pr;
+        hs->sc = o.pc;
+        hs->im = o.img;
+        hs->nn = o.nn;
+      }
+      ia_stores_done();
+      if (lane == 0) __hip_atomic_store(&hs->seq, nx.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    return;
+  }
+  if (!on) return;
+  QHand h;
+  h.r0 = px.r;
+  h.c0 = px.c;
+  h.v0 = mo.v;
+  h.s0r = __builtin_amdgcn_readfirstlane(mo.pr);
+  h.s0c = __builtin_amdgcn_readfirstlane(mo.pc);
+  h.i0 = __builtin_amdgcn_readfirstlane(mo.img);
+  h.n0 = __builtin_amdgcn_readfirstlane(mo.nn);
+  gather_wave_post<KS>(g, nx, jp, 0, mn, lane, ma.db64, gq, h, __builtin_amdgcn_readfirstlane(mo.src_lane),
+                       __builtin_amdgcn_readfirstlane(mo.app_lane), gw);
+}
+
+template <int RPL, bool PR, bool XO, class JS, bool GW = false>
 __device__ __forceinline__ void merge_gather_body(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const MergeArgs &ma,
                                                   const JS &jobs, Imgs B, const NextStep &nx) {
   constexpr int KS = 4;
-  const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * IA_PQ_WPB + (threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  static_assert(!GW || (PR && !XO && JS::single && IA_PQ_WPB == 1), "two-wave form: the one-job pruned early path");
+  const int w = __builtin_amdgcn_readfirstlane(GW ? blockIdx.x : blockIdx.x * IA_PQ_WPB + (threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63, wv = GW ? 0 : threadIdx.x >> 6;
   const int J = JS::single ? 1 : sd.J, JM = J * sd.M;
   __shared__ double qsh[IA_PQ_WPB][Geo<1>::DS], wsh[IA_PQ_WPB][Geo<1>::DS];
   __shared__ int crsh[IA_PQ_WPB][IA_WAVE];
   __shared__ float cvsh[IA_PQ_WPB][IA_WAVE];
   __shared__ __attribute__((aligned(16))) _Float16 xh[IA_PQ_WPB][2][16 * KS];  // owner publish: hi / lo columns
+  if constexpr (GW) {
+    const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w < JM) {  // (workgroup-uniform)
+      merge_gather_pair<RPL>(g, sd, A, ma, jobs.get(0), B, nx, w, role, lane, qsh[0], wsh[0], crsh[0], cvsh[0]);
+      return;
+    }
+    if (role) return;
+  }
   if (XO && w >= JM + J + (nx.sn.Mpad - J * nx.sn.M)) {  // the waiter (nx.wait_n > 0 only)
     // after an earlier timeout of this context: no waiting (one lost peer costs one timeout)
     if (__hip_atomic_load(nx.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
@@ -469,14 +557,14 @@ __device__ __forceinline__ void merge_gather_body(const LevelGeo &g, const StepD
   unsigned long long gs[5] = {__builtin_amdgcn_s_memtime(), 0, 0, 0, 0}, gst[5] = {0, 0, 0, 0, 0};
   const bool gprobe = w == sd.M / 2 && (sd.t % 256) == 128 && JM == sd.M;
 #endif
-  if (w < JM) {
+  if (!GW && w < JM) {  // (GW: merge_gather_pair above)
     const QPix px = ia_qpix(sd, g.bw, w);
     job = px.job;
     const JobPtrs jp = jobs.get(job);
     MergeOut o;
     if (px.c + 1 < g.bw) mn = job * nx.sn.M + (px.r - nx.sn.r0);
     const Imgs Bj = JS::single ? B : job_imgs(B, jp);
-    auto pre = [&]() {
+    auto pre = [&](int) {
       if (PR && nx.prefetch && mn >= 0) pf = qpre_load(g, nx.sn, Bj, jp, mn, lane);
     };
     merge_fused<1, RPL>(g, sd, A, ma, w, jp, px, qsh[wv], wsh[wv], crsh[wv], cvsh[wv], &o, pre);
@@ -582,11 +670,13 @@ __device__ __forceinline__ void merge_gather_body(const LevelGeo &g, const StepD
            gst[4] - gst[3]);
 #endif
 }
-template <int RPL, bool PR, bool XO, class JS>
-__global__ void __launch_bounds__(IA_PQ_WG) k_merge_gather(LevelGeo g, StepDesc sd, Imgs A, MergeArgs ma, JS jobs,
-                                                         Imgs B, NextStep nx) {
+template <int RPL, bool PR, bool XO, class JS, bool GW = false>
+__global__ void __launch_bounds__(GW ? 2 * IA_WAVE : IA_PQ_WG)
+k_merge_gather(LevelGeo g, StepDesc sd, Imgs A, MergeArgs ma, JS jobs, Imgs B, NextStep nx) {
   const unsigned long long t0 = ma.stamp ? ia_clock() : 0ull;  // option "stamps"
-  merge_gather_body<RPL, PR, XO, JS>(g, sd, A, ma, jobs, B, nx);
+  merge_gather_body<RPL, PR, XO, JS, GW>(g, sd, A, ma, jobs, B, nx);
+  // (GW: both waves stamp their workgroup's slot; the one that ends last, thousands of ticks after
+  // the other, leaves the end time)
   if (ma.stamp && (threadIdx.x & 63) == 0) ia_stamp_wg(ma.stamp, t0);
 }
 
@@ -612,55 +702,65 @@ void ia_launch_merge(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const
 
 // Every k_merge_gather instance the library launches, by what selects it: the one list both the
 // launcher and the chained-wave budget (ia_merge_gather_occupancy) read.  Owner-computes steps
-// (xo) exist only as one-job pruned steps.
+// (xo) exist only as one-job pruned steps, the two-wave form (gw, option "gather_wave") only as
+// the one-job, one-rank pruned early path.
 struct MergeGatherInst {
-  bool single, pruned, xo;
+  bool single, pruned, xo, gw;
   const void *fn;
+  int threads() const { return gw ? 2 * IA_WAVE : IA_PQ_WG; }
 };
 static const MergeGatherInst k_merge_gather_insts[] = {
-    {true, true, true, (const void *)k_merge_gather<4, true, true, JobArg1>},
-    {true, true, false, (const void *)k_merge_gather<4, true, false, JobArg1>},
-    {true, false, false, (const void *)k_merge_gather<4, false, false, JobArg1>},
-    {false, true, false, (const void *)k_merge_gather<4, true, false, JobArgN>},
-    {false, false, false, (const void *)k_merge_gather<4, false, false, JobArgN>},
+    {true, true, true, false, (const void *)k_merge_gather<4, true, true, JobArg1>},
+    {true, true, false, false, (const void *)k_merge_gather<4, true, false, JobArg1>},
+    {true, true, false, true, (const void *)k_merge_gather<4, true, false, JobArg1, true>},
+    {true, false, false, false, (const void *)k_merge_gather<4, false, false, JobArg1>},
+    {false, true, false, false, (const void *)k_merge_gather<4, true, false, JobArgN>},
+    {false, false, false, false, (const void *)k_merge_gather<4, false, false, JobArgN>},
 };
 
 void ia_launch_merge_gather(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const MergeArgs &ma, const JobSet &jobs,
                             const Imgs &B, const NextStep &nx, bool pruned, hipStream_t st) {
   // waves: the step's merges, each job's entering row, the next step's pad queries (+ the waiter)
   const int nw = sd.J * sd.M + sd.J + (nx.sn.Mpad - sd.J * nx.sn.M) + (nx.wait_n > 0 ? 1 : 0);
-  const dim3 grid(cdiv(nw, IA_PQ_WPB));
   const bool single = jobs.J == 1;
   const bool xo = single && pruned && (nx.xp.W > 0 || nx.wait_n > 0);
+  // two waves per workgroup: where the level reserved them (nx.gwave) and the early path runs
+  const bool gw = nx.gwave && single && pruned && !xo && !nx.kslot && nx.prefetch && nx.early;
   for (const MergeGatherInst &k : k_merge_gather_insts) {
-    if (k.single != single || k.pruned != pruned || k.xo != xo) continue;
+    if (k.single != single || k.pruned != pruned || k.xo != xo || k.gw != gw) continue;
+    const dim3 grid(gw ? nw : cdiv(nw, IA_PQ_WPB));
     // the kernel's arguments in order; the JS argument by the instance's kind (with_jobs' pairs)
     JobArg1 j1{jobs.j0};
     JobArgN jn{jobs.rest};
     Imgs Bj = single ? job0_imgs(B, jobs) : B;
     void *args[] = {(void *)&g,  (void *)&sd, (void *)&A, (void *)&ma, single ? (void *)&j1 : (void *)&jn,
                     (void *)&Bj, (void *)&nx};
-    (void)hipLaunchKernel(k.fn, grid, dim3(IA_PQ_WG), args, 0, st);
+    (void)hipLaunchKernel(k.fn, grid, dim3(k.threads()), args, 0, st);
     return;
   }
 }
-// the chained-wave budget's inputs (ia_capi.cpp, ia_chain_budget): over every k_merge_gather
-// instance the library launches, the most VGPRs per lane and the fewest workgroups per CU the
-// occupancy API admits, from the compiled kernels themselves
+// the chained-wave budget's inputs (ia_capi.cpp, ia_chain_budget): the most VGPRs per lane over
+// every k_merge_gather instance the library launches, and the workgroups per CU the occupancy
+// API admits and the workgroup size of the instance with the fewest resident waves per CU, from
+// the compiled kernels themselves
 void ia_merge_gather_occupancy(int *vgprs, int *blocks_per_cu, int *wg_threads) {
-  int vmax = 0, bmin = 1 << 30;
+  int vmax = 0, wmin = 1 << 30;
+  *blocks_per_cu = 0;
+  *wg_threads = IA_PQ_WG;
   for (const MergeGatherInst &k : k_merge_gather_insts) {
     hipFuncAttributes fa;
     int nb = 0;
     if (hipFuncGetAttributes(&fa, k.fn) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, IA_PQ_WG, 0) != hipSuccess) {
-      bmin = 0;
-      continue;
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, k.threads(), 0) != hipSuccess)
+      nb = 0;
+    else
+      vmax = std::max(vmax, (int)fa.numRegs);
+    const int waves = nb * (k.threads() / IA_WAVE);
+    if (waves < wmin) {
+      wmin = waves;
+      *blocks_per_cu = nb;
+      *wg_threads = k.threads();
     }
-    vmax = std::max(vmax, (int)fa.numRegs);
-    bmin = std::min(bmin, nb);
   }
   *vgprs = vmax;
-  *blocks_per_cu = bmin;
-  *wg_threads = IA_PQ_WG;
 }

@@ -217,6 +217,20 @@ int ia_version(void);
  * before waiting for that handoff: the other 54 features, fragments, projection and |q'|^2 sums,
  * and U' over the candidate rows requested first; U' then leaves out the row above's own two
  * candidates (a valid bound either way).
+ * "gather_wave" = 1 (default) / 0: that early path (one job, one rank, pruned level, options
+ * prefetch_next and early_gather on, fuse_sort not engaged) runs workgroups of two waves: wave 0
+ * merges the step-t pixel and nothing else, wave 1 gathers the next query beside it from wave
+ * start and takes the merged pixel through LDS for its late part (the pixel's two U' candidate
+ * rows, its window slots; then the row above's handoff as before).  Those two rows are the raster
+ * successors of rows the merge wave's lanes hold, posted through LDS as soon as they are placed:
+ * the gather wave loads every lane's successor during the merge and picks the two winners' by
+ * lane, so no dependent row load follows the merge (a winner from an overflow candidate or a
+ * certification rescan takes that load).  Same U' candidate rows as early_gather; only the
+ * summation order of the own pixel's terms differs.  Such a level reserves
+ * TWICE its waves of the chained-wave budget; where that is refused it runs the one-wave launches
+ * with the single reservation, and where that is refused too, separate launches
+ * (ia_chain_choice).  0, or any other merge + gather form (batched jobs, owner-computes,
+ * fuse_sort, unpruned levels): the one-wave launches.
  * "scan_wgs" = 8..256 (a multiple of 8; default 256, one per CU): workgroups of the context's
  * split-f16 scans (pruned: one chunk of DB tiles each; unpruned: contiguous tile ranges).  bench.py
  * gives the coarser pipelined levels' contexts 128, so their scans never queue for the whole GPU
@@ -340,6 +354,12 @@ int ia_merge_winners(const double *dist, const int64_t *row, int world, int64_t 
  * 1/16, from the compiled kernel's VGPRs per lane, the occupancy API's workgroups per CU and its
  * workgroup size; 0 = never chain.  ia_init computes it from k_merge_gather itself. */
 int ia_chain_budget(int n_cu, int vgprs, int api_blocks_per_cu, int wg_threads);
+/* What a level takes of that budget.  level_waves: the one-wave workgroups of its widest fused
+ * launch; in_flight: waves already reserved in the process; two_wave: the level qualifies for
+ * option "gather_wave".  Returns 2 (two-wave workgroups, 2 x level_waves reserved: they fit in
+ * budget - in_flight), 1 (one-wave workgroups, level_waves reserved) or 0 (neither fits, or no
+ * budget: separate merge and gather launches, nothing reserved). */
+int ia_chain_choice(int level_waves, int in_flight, int budget, int two_wave);
 /* Wavefront schedule of a level (t = col + 3*row): number of steps and max queries per step. */
 int ia_wavefront_shape(int h, int w, int64_t *steps, int64_t *max_queries);
 /* Pixels of step t: rows r0 .. r0+M-1, pixel (r, t - 3r).  Used by the level driver. */
