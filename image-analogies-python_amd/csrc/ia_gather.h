@@ -23,11 +23,39 @@ struct QHand {
   int s0r = 0, s0c = 0, i0 = 0, s1r = 0, s1c = 0, i1 = 0;
   int n0 = -1, n1 = -1;  // their exact NN rows (option "nn_bound")
 };
+// B' slot k < 12 (feature 43 + k) of the causal 5x5 window at (r, c): its pixel (y, x), reflected
+// at the image's borders (so one pixel can fill several slots)
+__device__ __forceinline__ void bslot(const Imgs &B, int k, int r, int c, int &y, int &x) {
+  y = ia_reflect(r + k / 5 - 2, B.h);
+  x = ia_reflect(c + k % 5 - 2, B.w);
+}
+// This lane's causal neighbour of the query pixel (r, c), raster index qi: lanes 0..14 carry
+// neighbour k of the causal 5x5 (product(rows, cols) order as merge_fused) for its source pixel;
+// lanes 15..29, where nnl (the level keeps exact NN rows, option "nn_bound"), the same neighbour
+// k = lane - 15 for its NN row.  ok: the lane carries one, inside B and before qi in raster order.
+struct CausalNb {
+  int k, nr, nc, nb;  // neighbour, its pixel and raster index
+  bool ok;
+};
+__device__ __forceinline__ CausalNb causal_nb(const LevelGeo &g, int r, int c, int qi, int lane, bool nnl) {
+  CausalNb n{0, 0, 0, 0, false};
+  if (qi > 0 && (lane < 15 || nnl)) {
+    n.k = lane < 15 ? lane : lane - 15;
+    n.nr = r - 2 + n.k / 5;
+    n.nc = c - 2 + n.k % 5;
+    if (n.nr >= 0 && n.nc >= 0 && n.nc < g.bw && n.nr * g.bw + n.nc < qi) {
+      n.nb = n.nr * g.bw + n.nc;
+      n.ok = true;
+    }
+  }
+  return n;
+}
 template <bool FUSE>
 __device__ __forceinline__ double feat_q1(const Imgs &B, int f, int r, int c, const QHand &h) {
   if constexpr (FUSE) {
     if (f >= 43) {  // the B' part (causal 5x5 at (r, c), k < 12)
-      const int k = f - 43, y = ia_reflect(r + k / 5 - 2, B.h), x = ia_reflect(c + k % 5 - 2, B.w);
+      int y, x;
+      bslot(B, f - 43, r, c, y, x);
       if (y == h.r0 && x == h.c0) return h.v0;
       if (y == h.r1 && x == h.c1) return h.v1;
       return B.p3[(int64_t)y * B.w + x];
@@ -104,6 +132,63 @@ __device__ __forceinline__ void sorted_publish(const NextStep &nx, int m, int la
   if (c < 4 * KS) reinterpret_cast<h16x8 *>(nx.sfrag)[((int64_t)qt * 2 * KS + 2 * sp + part) * IA_WAVE + h * IA_TILE + j] = v;
   if (lane < 3) nx.sinfo[3 * x + lane] = sel3(lane, i0, i1, i2);
   if (lane == 3) nx.sorder[x] = m;
+}
+
+// The bounded wait for a row's handoff slot (k_merge_gather: written by the wave of this launch
+// that merged the row's step-t pixel): until its seq is the step's.  relaxed: the slot is uncached
+// (nothing stale to invalidate); its fields load after the seq was seen.  A slot that does not
+// arrive within nx.timeout_ticks sets err bit 16.
+__device__ __forceinline__ void handoff_wait(const HandSlot *hs, const NextStep &nx) {
+  const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
+  while (__hip_atomic_load(&hs->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != nx.seq) {
+    if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > nx.timeout_ticks) {
+      atomicOr(nx.err, 16u);
+      break;
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
+
+// Phase stamp of the IA_PROBE & 8 diagnostic builds, on the sampled wave only (on): gst[k] = the
+// clock once everything issued so far has completed
+#if IA_PROBE & 8
+#define IA_GST(on, gst, k) do { if (on) { __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); \
+                                          (gst)[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
+#else
+#define IA_GST(on, gst, k) do { } while (0)
+#endif
+
+// The pruning record (uniform values) of a query with |q'|^2 = ss, projections p and exact U'
+// candidate distance u (DBL_MAX: no candidate); ksc the key scale, ufac the level's U' factor.
+// o0 / o1: the projection interval; o2: U' and the Morton key, and K3p's hi x hi block filter
+// bound (k3p_variant 14/15, ia_k3h.hip k3p_filtered): value bound
+// z >= U' - |q'|^2 with the f32 rounding of z and of the kernel's lim = z + R_t (...)
+// (2^-22 (|q'|^2 + U')) and the subnormal / norm-column terms (2^-24 (16 |q'| + 300));
+// w = 2^-8 |q'| (twice the relative error term's |q'| part)
+__device__ __forceinline__ void prune_record(double ss, const double (&pp)[IA_NPC], double u, const double *ksc, double ufac,
+                                             float4 &o0, float4 &o1, float4 &o2) {
+  const double p[IA_NPC] = {pp[0], pp[1], pp[2], pp[3]};  // (a copy: the caller's array stays in registers)
+  const double qn = sqrt(ss);
+  const bool fin = u < DBL_MAX;
+  const unsigned key = fin ? prune_key(p, ksc) : IA_PRUNE_KEY_INF;
+  const float up = fin ? round_up_f(u * ufac) : INFINITY;
+  const float z = fin ? round_up_f((double)up - ss + 0x1p-22 * (ss + (double)up) + 0x1p-24 * (16.0 * qn + 300.0)) : INFINITY;
+  const float w = round_up_f(0x1p-8 * qn * (1.0 + 0x1p-40));
+  o0 = make_float4(round_down_f(p[0] - IA_PRUNE_MABS), round_down_f(p[1] - IA_PRUNE_MABS), round_down_f(p[2] - IA_PRUNE_MABS),
+                   round_down_f(p[3] - IA_PRUNE_MABS));
+  o1 = make_float4(round_up_f(p[0] + IA_PRUNE_MABS), round_up_f(p[1] + IA_PRUNE_MABS), round_up_f(p[2] + IA_PRUNE_MABS),
+                   round_up_f(p[3] + IA_PRUNE_MABS));
+  o2 = make_float4(up, __uint_as_float(key), z, w);
+}
+// query m's |q'|^2 and pruning record, from lane 0
+__device__ __forceinline__ void prune_record_store(int lane, int m, double *qn2, float4 *qinfo, double ss, const float4 &o0,
+                                                   const float4 &o1, const float4 &o2) {
+  if (lane == 0) {
+    qn2[m] = ss;
+    qinfo[3 * m] = o0;
+    qinfo[3 * m + 1] = o1;
+    qinfo[3 * m + 2] = o2;
+  }
 }
 
 // K2p's pad query m >= J M: zero fragments, an empty pruning record
@@ -184,13 +269,7 @@ __device__ __forceinline__ void gather_p_query(const LevelGeo &g, const StepDesc
                                                _Float16 *xh1, const QHand &h, float4 &o0, float4 &o1, float4 &o2,
                                                const QPre &pf = QPre{}, unsigned long long *gst = nullptr) {
   constexpr int D = 55, KD = 16 * KS;
-#if IA_PROBE & 8
-#define IA_GST(k) do { if (gst) { __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); \
-                       gst[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define IA_GST(k) do { (void)gst; } while (0)
-#endif
-  IA_GST(0);
+  IA_GST(gst, gst, 0);
   static_assert(KD <= IA_WAVE, "one feature per lane");
   const QPix px = ia_qpix(sd, g.bw, m);
   const int32_t *__restrict__ s = jp.s, *__restrict__ im = jp.im;
@@ -202,11 +281,10 @@ __device__ __forceinline__ void gather_p_query(const LevelGeo &g, const StepDesc
   // out-of-range or missing one is skipped); only its tightness depends on them.
   int crow = -1;
   const bool nnl = jp.nn && lane >= 15 && lane < 30;
-  if (qi > 0 && (lane < 15 || nnl)) {
-    const int k = lane < 15 ? lane : lane - 15;
-    const int nr = r - 2 + k / 5, nc = c - 2 + k % 5;
-    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < qi) {
-      const int nb = nr * g.bw + nc;
+  {
+    const CausalNb n = causal_nb(g, r, c, qi, lane, nnl);
+    const int nr = n.nr, nc = n.nc, nb = n.nb;
+    if (n.ok) {
       int sr = 0, sc = 0, si = 0, nnrow = -1;
       if (!nnl) {
         if (FUSE && nr == h.r0 && nc == h.c0) {
@@ -236,7 +314,8 @@ __device__ __forceinline__ void gather_p_query(const LevelGeo &g, const StepDesc
       if (pf.on) {  // prefetched; the B' part substituted at the two step-t pixels
         v = pf.v;
         if (FUSE && f >= 43) {
-          const int k = f - 43, y = ia_reflect(r + k / 5 - 2, B.h), x = ia_reflect(c + k % 5 - 2, B.w);
+          int y, x;
+      bslot(B, f - 43, r, c, y, x);
           v = (y == h.r0 && x == h.c0) ? h.v0 : (y == h.r1 && x == h.c1) ? h.v1 : v;
         }
       } else {
@@ -255,40 +334,19 @@ __device__ __forceinline__ void gather_p_query(const LevelGeo &g, const StepDesc
       if (xh0) split_h(f == D ? IA_NORM_SCALE : 0., xh0[f], xh1[f]);
     }
   }
-  IA_GST(1);
+  IA_GST(gst, gst, 1);
   ss = wave_sum_d(ss);
 #pragma unroll
   for (int i = 0; i < IA_NPC; i++) p[i] = wave_sum_d_x(p[i]);
-  IA_GST(2);
+  IA_GST(gst, gst, 2);
   __builtin_amdgcn_wave_barrier();  // qsh written by this wave's lanes, read below
   double u = DBL_MAX;
   if (crow >= 0) u = exact_dist_level<1>(db64, crow, qsh);
   u = wave_min_d_x(u);
-  IA_GST(3);
-  // the pruning record (uniform values): projection interval, U' and the Morton key, and K3p's
-  // hi x hi block filter bound (k3p_variant 14/15, ia_k3h.hip k3p_filtered): value bound
-  // z >= U' - |q'|^2 with the f32 rounding of z and of the kernel's lim = z + R_t (...)
-  // (2^-22 (|q'|^2 + U')) and the subnormal / norm-column terms (2^-24 (16 |q'| + 300));
-  // w = 2^-8 |q'| (twice the relative error term's |q'| part)
-  const double qn = sqrt(ss);
-  const bool fin = u < DBL_MAX;
-  const unsigned key = fin ? prune_key(p, basis + IA_NPC * D) : IA_PRUNE_KEY_INF;
-  const float up = fin ? round_up_f(u * ufac) : INFINITY;
-  const float z = fin ? round_up_f((double)up - ss + 0x1p-22 * (ss + (double)up) + 0x1p-24 * (16.0 * qn + 300.0)) : INFINITY;
-  const float w = round_up_f(0x1p-8 * qn * (1.0 + 0x1p-40));
-  o0 = make_float4(round_down_f(p[0] - IA_PRUNE_MABS), round_down_f(p[1] - IA_PRUNE_MABS), round_down_f(p[2] - IA_PRUNE_MABS),
-                   round_down_f(p[3] - IA_PRUNE_MABS));
-  o1 = make_float4(round_up_f(p[0] + IA_PRUNE_MABS), round_up_f(p[1] + IA_PRUNE_MABS), round_up_f(p[2] + IA_PRUNE_MABS),
-                   round_up_f(p[3] + IA_PRUNE_MABS));
-  o2 = make_float4(up, __uint_as_float(key), z, w);
-  if (lane == 0) {
-    qn2[m] = ss;
-    qinfo[3 * m] = o0;
-    qinfo[3 * m + 1] = o1;
-    qinfo[3 * m + 2] = o2;
-  }
-  IA_GST(4);
-#undef IA_GST
+  IA_GST(gst, gst, 3);
+  prune_record(ss, p, u, basis + IA_NPC * D, ufac, o0, o1, o2);
+  prune_record_store(lane, m, qn2, qinfo, ss, o0, o1, o2);
+  IA_GST(gst, gst, 4);
 }
 // K2h's work for one query m of step sd (unpruned split-f16 levels), with the fused gather's
 // two step-t pixels substituted (QHand) in the B' part
@@ -306,7 +364,8 @@ __device__ __forceinline__ void gather_h_query_fused(const LevelGeo &g, const St
     if (f < D) {
       double v;
       if (f >= 43) {  // the B' part (causal 5x5 at (r, c), k < 12)
-        const int k = f - 43, y = ia_reflect(r + k / 5 - 2, B.h), x = ia_reflect(c + k % 5 - 2, B.w);
+        int y, x;
+      bslot(B, f - 43, r, c, y, x);
         v = (y == h.r0 && x == h.c0) ? h.v0 : (y == h.r1 && x == h.c1) ? h.v1 : B.p3[(int64_t)y * B.w + x];
       } else {
         v = feat<1>(B, f, r, c, 0);
@@ -343,6 +402,52 @@ __device__ __forceinline__ QConst qconst_load(const NextStep &nx, int lane) {
   return k;
 }
 
+// The pieces the early gathers share (gather_p_early; the two-wave form below).
+// A U' candidate row requested (row 0 where the lane has none: the loads are unconditional) ...
+using GatherRow = double2[Geo<1>::DS / 2];
+__device__ __forceinline__ void gather_row_load(const double *__restrict__ db64, int crow, GatherRow &rowv) {
+  constexpr int DS = Geo<1>::DS;
+  const double2 *src = reinterpret_cast<const double2 *>(db64 + (int64_t)(crow >= 0 ? crow : 0) * DS);
+#pragma unroll
+  for (int i = 0; i < DS / 2; i++) rowv[i] = src[i];
+}
+// ... and its U' partial distance over the non-late features (pairwise order; a late feature, mask
+// lm, adds 0) with the row's values at the twelve B' slots (read after a handoff for the late ones)
+__device__ __forceinline__ void gather_row_part(const GatherRow &rowv, const double *qsh, unsigned long long lm, double &part,
+                                                double *al) {
+  constexpr int D = 55;
+  const double *rv = reinterpret_cast<const double *>(rowv);
+  part = pw_sum<D>([&](int f) {
+    const double d = rv[f] - qsh[f];
+    return ((lm >> f) & 1ull) ? 0. : d * d;
+  });
+#pragma unroll
+  for (int k = 0; k < 12; k++) al[k] = rv[43 + k];
+}
+__device__ __forceinline__ void gather_wave_row(const double *__restrict__ db64, int crow, const double *qsh,
+                                                unsigned long long lm, double &part, double *al) {
+  GatherRow rowv;
+  gather_row_load(db64, crow, rowv);
+  gather_row_part(rowv, qsh, lm, part, al);
+}
+// One late pixel's slots (mask lm, value v; qc: its centred value in the slots' lanes), in slot
+// order: its terms of |q'|^2, the projections (bas: the lanes' basis columns) and this lane's U'
+// distance (al: its row's values at the B' slots)
+__device__ __forceinline__ void gather_late_slots(unsigned long long lm, double v, double qc, const double (&bas)[IA_NPC],
+                                                  const double *al, double &ss, double *p, double &part) {
+#pragma unroll
+  for (int k = 0; k < 12; k++) {
+    if ((lm >> (43 + k)) & 1ull) {  // wave-uniform
+      const double qcl = readlane_d(qc, 43 + k);
+      ss += qcl * qcl;
+#pragma unroll
+      for (int i = 0; i < IA_NPC; i++) p[i] += readlane_d(bas[i], 43 + k) * qcl;
+      const double d = al[k] - v;
+      part += d * d;
+    }
+  }
+}
+
 // The fused gather of query mn (step t + 1) for a merge wave of a one-rank pruned level (option
 // "prefetch_next"; no publish): everything that does not depend on the row above's step-t result
 // runs BEFORE the wait for its handoff - the query's other 54 features (q64, split-f16 fragments,
@@ -358,15 +463,11 @@ template <int KS>
 __device__ __forceinline__ void gather_p_early(const LevelGeo &g, const NextStep &nx, const Imgs &B, const JobPtrs &jp,
                                                int job, int mn, int lane, const double *__restrict__ db64, double *qsh,
                                                const QHand &h0, const QPre &pf, const QConst &qk) {
-  constexpr int D = 55, KD = 16 * KS, DS = Geo<1>::DS;
+  constexpr int D = 55, KD = 16 * KS;
   static_assert(KD <= IA_WAVE, "one feature per lane");
 #if IA_PROBE & 8
   unsigned long long gst[7] = {__builtin_amdgcn_s_memtime(), 0, 0, 0, 0, 0, 0};
   const bool gprobe = mn == nx.sn.M / 2 && (nx.sn.t % 256) == 129;
-#define IA_GST2(k) do { if (gprobe) { __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); \
-                        gst[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define IA_GST2(k) do { } while (0)
 #endif
   const StepDesc &sn = nx.sn;
   const QPix pn = ia_qpix(sn, g.bw, mn);
@@ -380,7 +481,8 @@ __device__ __forceinline__ void gather_p_early(const LevelGeo &g, const NextStep
   if (lane < D) {
     v = pf.v;
     if (lane >= 43) {
-      const int k = lane - 43, y = ia_reflect(r + k / 5 - 2, B.h), x = ia_reflect(c + k % 5 - 2, B.w);
+      int y, x;
+      bslot(B, lane - 43, r, c, y, x);
       if (y == h0.r0 && x == h0.c0) v = h0.v0;
       late = above && y == ar && x == ac;
     }
@@ -392,10 +494,10 @@ __device__ __forceinline__ void gather_p_early(const LevelGeo &g, const NextStep
   // "nn_bound") their shifted NN rows; the row above's pixel skipped (its result is late)
   int crow = -1;
   const bool nnl = jp.nn && lane >= 15 && lane < 30;
-  if (qi > 0 && (lane < 15 || nnl)) {
-    const int k = lane < 15 ? lane : lane - 15;
-    const int nr = r - 2 + k / 5, nc = c - 2 + k % 5;
-    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < qi && !(above && nr == ar && nc == ac)) {
+  {
+    const CausalNb n = causal_nb(g, r, c, qi, lane, nnl);
+    const int nr = n.nr, nc = n.nc;
+    if (n.ok && !(above && nr == ar && nc == ac)) {
       const bool own = nr == h0.r0 && nc == h0.c0;
       const int sr = own ? h0.s0r : pf.sr, sc = own ? h0.s0c : pf.sc, si = own ? h0.i0 : pf.si;
       const int nnrow = own ? h0.n0 : pf.nn;
@@ -403,12 +505,8 @@ __device__ __forceinline__ void gather_p_early(const LevelGeo &g, const NextStep
     }
   }
   // the candidate row, requested now (in flight during the feature work below)
-  double2 rowv[DS / 2];
-  {
-    const double2 *src = reinterpret_cast<const double2 *>(db64 + (int64_t)(crow >= 0 ? crow : 0) * DS);
-#pragma unroll
-    for (int i = 0; i < DS / 2; i++) rowv[i] = src[i];
-  }
+  GatherRow rowv;
+  gather_row_load(db64, crow, rowv);
   if (lane < D) qsh[lane] = late ? 0. : v;
   // ---- the non-late features: q64, fragments, projections, |q'|^2 (late lanes hold 0)
   double ss = 0., p[IA_NPC] = {0., 0., 0., 0.}, qc = 0.;
@@ -429,33 +527,20 @@ __device__ __forceinline__ void gather_p_early(const LevelGeo &g, const NextStep
   ss = wave_sum_d_x(ss);
 #pragma unroll
   for (int i = 0; i < IA_NPC; i++) p[i] = wave_sum_d_x(p[i]);
-  IA_GST2(1);
+  IA_GST(gprobe, gst, 1);
   __builtin_amdgcn_wave_barrier();  // qsh written by this wave's lanes, read below
   // ---- U' partial distances over the non-late features (pairwise order; a late feature adds 0)
-  const double *rv = reinterpret_cast<const double *>(rowv);
-  double part = pw_sum<D>([&](int f) {
-    const double d = rv[f] - qsh[f];
-    return ((lm >> f) & 1ull) ? 0. : d * d;
-  });
-  double al[12];  // the row's values at the B' slots (read after the handoff for the late ones)
-#pragma unroll
-  for (int k = 0; k < 12; k++) al[k] = rv[43 + k];
-  IA_GST2(2);
+  double part, al[12];
+  gather_row_part(rowv, qsh, lm, part, al);
+  IA_GST(gprobe, gst, 2);
   // ---- the row above's result (handoff)
   QHand h = h0;
   if (above) {
     const HandSlot *hs = nx.hand + (int64_t)job * g.bh + ar;
-    const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-    while (__hip_atomic_load(&hs->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != nx.seq) {
-      if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > nx.timeout_ticks) {
-        atomicOr(nx.err, 16u);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
+    handoff_wait(hs, nx);
     h.v1 = hs->v;
   }
-  IA_GST2(3);
+  IA_GST(gprobe, gst, 3);
   // ---- the late slots: their value, fragments and terms, in slot order
   if (lm) {
     if (late) {
@@ -463,48 +548,20 @@ __device__ __forceinline__ void gather_p_early(const LevelGeo &g, const NextStep
       qc = h.v1 - qk.mu;
       put_qh<KS>((_Float16 *)nx.qf, mn, lane, -2.0 * qc);
     }
-#pragma unroll
-    for (int k = 0; k < 12; k++) {
-      if ((lm >> (43 + k)) & 1ull) {  // wave-uniform
-        const double qcl = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(qc), 43 + k),
-                                            __builtin_amdgcn_readlane(__double2loint(qc), 43 + k));
-        ss += qcl * qcl;
-#pragma unroll
-        for (int i = 0; i < IA_NPC; i++) {
-          const double bl = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(qk.bas[i]), 43 + k),
-                                             __builtin_amdgcn_readlane(__double2loint(qk.bas[i]), 43 + k));
-          p[i] += bl * qcl;
-        }
-        const double d = al[k] - h.v1;
-        part += d * d;
-      }
-    }
+    gather_late_slots(lm, h.v1, qc, qk.bas, al, ss, p, part);
   }
   double u = crow >= 0 ? part : DBL_MAX;
   u = wave_min_d_x(u);
-  IA_GST2(4);
-  // ---- the pruning record (gather_p_query's, from these sums)
-  const double qn = sqrt(ss);
-  const bool fin = u < DBL_MAX;
-  const unsigned key = fin ? prune_key(p, qk.sc) : IA_PRUNE_KEY_INF;
-  const float up = fin ? round_up_f(u * nx.ufac) : INFINITY;
-  const float z = fin ? round_up_f((double)up - ss + 0x1p-22 * (ss + (double)up) + 0x1p-24 * (16.0 * qn + 300.0)) : INFINITY;
-  const float w = round_up_f(0x1p-8 * qn * (1.0 + 0x1p-40));
-  if (lane == 0) {
-    nx.qn2[mn] = ss;
-    nx.qinfo[3 * mn] = make_float4(round_down_f(p[0] - IA_PRUNE_MABS), round_down_f(p[1] - IA_PRUNE_MABS),
-                                   round_down_f(p[2] - IA_PRUNE_MABS), round_down_f(p[3] - IA_PRUNE_MABS));
-    nx.qinfo[3 * mn + 1] = make_float4(round_up_f(p[0] + IA_PRUNE_MABS), round_up_f(p[1] + IA_PRUNE_MABS),
-                                       round_up_f(p[2] + IA_PRUNE_MABS), round_up_f(p[3] + IA_PRUNE_MABS));
-    nx.qinfo[3 * mn + 2] = make_float4(up, __uint_as_float(key), z, w);
-  }
-  IA_GST2(5);
+  IA_GST(gprobe, gst, 4);
+  float4 o0, o1, o2;
+  prune_record(ss, p, u, qk.sc, nx.ufac, o0, o1, o2);
+  prune_record_store(lane, mn, nx.qn2, nx.qinfo, ss, o0, o1, o2);
+  IA_GST(gprobe, gst, 5);
 #if IA_PROBE & 8
   if (gprobe && lane == 0)
     printf("ESTAMP bw=%d t=%d M=%d pre=%llu part=%llu handoff=%llu late=%llu rec=%llu\n", g.bw, sn.t, sn.M, gst[1] - gst[0],
            gst[2] - gst[1], gst[3] - gst[2], gst[4] - gst[3], gst[5] - gst[4]);
 #endif
-#undef IA_GST2
 }
 
 // The gather wave of a two-wave merge + gather workgroup (option "gather_wave", ia_kernels.hip
@@ -535,23 +592,6 @@ struct GatherWave {
   unsigned long long t0 = 0, t1 = 0, t2 = 0;
 #endif
 };
-// the U' partial distance of this lane's candidate row over the non-late features and the row's
-// values at the twelve B' slots
-__device__ __forceinline__ void gather_wave_row(const double *__restrict__ db64, int crow, const double *qsh,
-                                                unsigned long long lm, double &part, double *al) {
-  constexpr int D = 55, DS = Geo<1>::DS;
-  double2 rowv[DS / 2];
-  const double2 *src = reinterpret_cast<const double2 *>(db64 + (int64_t)(crow >= 0 ? crow : 0) * DS);
-#pragma unroll
-  for (int i = 0; i < DS / 2; i++) rowv[i] = src[i];
-  const double *rv = reinterpret_cast<const double *>(rowv);
-  part = pw_sum<D>([&](int f) {
-    const double d = rv[f] - qsh[f];
-    return ((lm >> f) & 1ull) ? 0. : d * d;
-  });
-#pragma unroll
-  for (int k = 0; k < 12; k++) al[k] = rv[43 + k];
-}
 template <int KS>
 __device__ __forceinline__ GatherWave gather_wave_pre(const LevelGeo &g, const NextStep &nx, const Imgs &B, const JobPtrs &jp,
                                                       int mn, int lane, const double *__restrict__ db64, double *qsh) {
@@ -568,7 +608,8 @@ __device__ __forceinline__ GatherWave gather_wave_pre(const LevelGeo &g, const N
   const bool above = r >= 1 && c + 2 < g.bw;
   const int ar = r - 1, ac = c + 2, orr = r, oc = c - 1;  // the two step-t pixels
   if (lane >= 43 && lane < D) {
-    const int k = lane - 43, y = ia_reflect(r + k / 5 - 2, B.h), x = ia_reflect(c + k % 5 - 2, B.w);
+    int y, x;
+    bslot(B, lane - 43, r, c, y, x);
     w.late0 = y == orr && x == oc;
     w.late1 = above && y == ar && x == ac;
   }
@@ -577,10 +618,10 @@ __device__ __forceinline__ GatherWave gather_wave_pre(const LevelGeo &g, const N
   const bool late = w.late0 || w.late1;
   // ---- U' candidate rows (gather_p_early's lanes); the two late pixels' skipped here
   const bool nnl = jp.nn && lane >= 15 && lane < 30;
-  if (qi > 0 && (lane < 15 || nnl)) {
-    const int k = lane < 15 ? lane : lane - 15;
-    const int nr = r - 2 + k / 5, nc = c - 2 + k % 5;
-    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < qi && !(above && nr == ar && nc == ac)) {
+  {
+    const CausalNb n = causal_nb(g, r, c, qi, lane, nnl);
+    const int nr = n.nr, nc = n.nc;
+    if (n.ok && !(above && nr == ar && nc == ac)) {
       if (nr == orr && nc == oc) w.own = true;
       else w.crow = ucand_row(g, r, c, nr, nc, nnl, pf.sr, pf.sc, pf.si, pf.nn);
     }
@@ -645,21 +686,6 @@ __device__ __forceinline__ void gather_wave_next(const LevelGeo &g, const NextSt
   w.t2 = __builtin_amdgcn_s_memtime();
 #endif
 }
-// one late pixel's slots (mask lm, value qc in the slots' lanes), in slot order: its terms of
-// |q'|^2, the projections and this lane's U' distance
-__device__ __forceinline__ void gather_wave_late(GatherWave &w, unsigned long long lm, double v) {
-#pragma unroll
-  for (int k = 0; k < 12; k++) {
-    if ((lm >> (43 + k)) & 1ull) {  // wave-uniform
-      const double qcl = readlane_d(w.qc, 43 + k);
-      w.ss += qcl * qcl;
-#pragma unroll
-      for (int i = 0; i < IA_NPC; i++) w.p[i] += readlane_d(w.qk.bas[i], 43 + k) * qcl;
-      const double d = w.al[k] - v;
-      w.part += d * d;
-    }
-  }
-}
 // h: the own pixel's result (r0, c0, v0, s0r, s0c, i0, n0) from the merge wave
 template <int KS>
 __device__ __forceinline__ void gather_wave_post(const LevelGeo &g, const NextStep &nx, const JobPtrs &jp, int job, int mn,
@@ -669,10 +695,6 @@ __device__ __forceinline__ void gather_wave_post(const LevelGeo &g, const NextSt
 #if IA_PROBE & 8
   unsigned long long gst[5] = {__builtin_amdgcn_s_memtime(), 0, 0, 0, 0};
   const bool gprobe = mn == nx.sn.M / 2 && (nx.sn.t % 256) == 129;
-#define IA_GST3(k) do { if (gprobe) { __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); \
-                        gst[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define IA_GST3(k) do { } while (0)
 #endif
   const QPix pn = ia_qpix(nx.sn, g.bw, mn);
   const int r = pn.r, c = pn.c;
@@ -704,55 +726,34 @@ __device__ __forceinline__ void gather_wave_post(const LevelGeo &g, const NextSt
     w.qc = h.v0 - w.qk.mu;
     put_qh<KS>((_Float16 *)nx.qf, mn, lane, -2.0 * w.qc);
   }
-  gather_wave_late(w, w.lm0, h.v0);
-  IA_GST3(1);
+  gather_late_slots(w.lm0, h.v0, w.qc, w.qk.bas, w.al, w.ss, w.p, w.part);
+  IA_GST(gprobe, gst, 1);
   // ---- the row above's result (handoff), then its late slots
   if (above) {
     const HandSlot *hs = nx.hand + (int64_t)job * g.bh + (r - 1);
-    const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-    while (__hip_atomic_load(&hs->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != nx.seq) {
-      if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > nx.timeout_ticks) {
-        atomicOr(nx.err, 16u);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
+    handoff_wait(hs, nx);
     const double v1 = hs->v;
-    IA_GST3(2);
+    IA_GST(gprobe, gst, 2);
     if (w.late1) {
       nx.q64[(int64_t)mn * D + lane] = v1;
       w.qc = v1 - w.qk.mu;
       put_qh<KS>((_Float16 *)nx.qf, mn, lane, -2.0 * w.qc);
     }
-    gather_wave_late(w, w.lm1, v1);
+    gather_late_slots(w.lm1, v1, w.qc, w.qk.bas, w.al, w.ss, w.p, w.part);
   } else {
-    IA_GST3(2);
+    IA_GST(gprobe, gst, 2);
   }
   double u = w.crow >= 0 ? w.part : DBL_MAX;
   u = wave_min_d_x(u);
-  IA_GST3(3);
-  // ---- the pruning record (gather_p_query's, from these sums)
-  const double ss = w.ss, qn = sqrt(ss);
-  const double(&p)[IA_NPC] = w.p;
-  const bool fin = u < DBL_MAX;
-  const unsigned key = fin ? prune_key(p, w.qk.sc) : IA_PRUNE_KEY_INF;
-  const float up = fin ? round_up_f(u * nx.ufac) : INFINITY;
-  const float z = fin ? round_up_f((double)up - ss + 0x1p-22 * (ss + (double)up) + 0x1p-24 * (16.0 * qn + 300.0)) : INFINITY;
-  const float wd = round_up_f(0x1p-8 * qn * (1.0 + 0x1p-40));
-  if (lane == 0) {
-    nx.qn2[mn] = ss;
-    nx.qinfo[3 * mn] = make_float4(round_down_f(p[0] - IA_PRUNE_MABS), round_down_f(p[1] - IA_PRUNE_MABS),
-                                   round_down_f(p[2] - IA_PRUNE_MABS), round_down_f(p[3] - IA_PRUNE_MABS));
-    nx.qinfo[3 * mn + 1] = make_float4(round_up_f(p[0] + IA_PRUNE_MABS), round_up_f(p[1] + IA_PRUNE_MABS),
-                                       round_up_f(p[2] + IA_PRUNE_MABS), round_up_f(p[3] + IA_PRUNE_MABS));
-    nx.qinfo[3 * mn + 2] = make_float4(up, __uint_as_float(key), z, wd);
-  }
-  IA_GST3(4);
+  IA_GST(gprobe, gst, 3);
+  float4 o0, o1, o2;
+  prune_record(w.ss, w.p, u, w.qk.sc, nx.ufac, o0, o1, o2);
+  prune_record_store(lane, mn, nx.qn2, nx.qinfo, w.ss, o0, o1, o2);
+  IA_GST(gprobe, gst, 4);
 #if IA_PROBE & 8
   if (gprobe && lane == 0)
     printf("WSTAMP bw=%d t=%d M=%d pre=%llu part=%llu wait_merge=%llu own=%llu handoff=%llu late=%llu rec=%llu\n", g.bw,
            nx.sn.t, nx.sn.M, w.t1 - w.t0, w.t2 - w.t1, gst[0] - w.t2, gst[1] - gst[0], gst[2] - gst[1], gst[3] - gst[2],
            gst[4] - gst[3]);
 #endif
-#undef IA_GST3
 }

@@ -21,6 +21,30 @@ struct MergeOut {  // one pixel's result: B' value (first channel), source pixel
   // holds it: the winner came from an overflow candidate or a certification rescan)
   int src_lane, app_lane;
 };
+// the fused merge + gather launch (k_merge_gather): pixel (r, c)'s result as its wave's next
+// query's own pixel
+__device__ __forceinline__ void qhand_own(QHand &h, int r, int c, const MergeOut &o) {
+  h.r0 = r;
+  h.c0 = c;
+  h.v0 = o.v;
+  h.s0r = o.pr;
+  h.s0c = o.pc;
+  h.i0 = o.img;
+  h.n0 = o.nn;
+}
+// ... and into its row's handoff slot for the row below (ia_gather.h handoff_wait): the fields,
+// store completion, then the step's seq
+__device__ __forceinline__ void handoff_publish(HandSlot *hs, const MergeOut &o, const NextStep &nx, int lane) {
+  if (lane == 0) {
+    hs->v = o.v;
+    hs->sr = o.pr;
+    hs->sc = o.pc;
+    hs->im = o.img;
+    hs->nn = o.nn;
+  }
+  ia_stores_done();
+  if (lane == 0) __hip_atomic_store(&hs->seq, nx.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // Fused single-rank merge of query m: certified exact NN + coherence + kappa + writeback.
 // Memory is touched in two dependent rounds: (1) the K3 records, the coherence neighbours'
@@ -484,18 +508,7 @@ __device__ __forceinline__ void merge_gather_pair(const LevelGeo &g, const StepD
   __syncthreads();
   if (role == 0) {
     // (after the barrier: the gather wave, long there, does not wait for these stores' completion)
-    if (px.r + 1 < g.bh && px.c >= 2) {  // row r + 1 gathers (r + 1, c - 2) at step t + 1
-      HandSlot *hs = nx.hand + px.r;
-      if (lane == 0) {
-        hs->v = o.v;
-        hs->sr = o.pr;
-        hs->sc = o.pc;
-        hs->im = o.img;
-        hs->nn = o.nn;
-      }
-      ia_stores_done();
-      if (lane == 0) __hip_atomic_store(&hs->seq, nx.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (px.r + 1 < g.bh && px.c >= 2) handoff_publish(nx.hand + px.r, o, nx, lane);  // for (r + 1, c - 2) of step t + 1
     return;
   }
   if (!on) return;
@@ -568,25 +581,9 @@ __device__ __forceinline__ void merge_gather_body(const LevelGeo &g, const StepD
       if (PR && nx.prefetch && mn >= 0) pf = qpre_load(g, nx.sn, Bj, jp, mn, lane);
     };
     merge_fused<1, RPL>(g, sd, A, ma, w, jp, px, qsh[wv], wsh[wv], crsh[wv], cvsh[wv], &o, pre);
-    if (px.r + 1 < g.bh && px.c >= 2) {  // row r + 1 gathers (r + 1, c - 2) at step t + 1
-      HandSlot *hs = nx.hand + (int64_t)job * g.bh + px.r;
-      if (lane == 0) {
-        hs->v = o.v;
-        hs->sr = o.pr;
-        hs->sc = o.pc;
-        hs->im = o.img;
-        hs->nn = o.nn;
-      }
-      ia_stores_done();
-      if (lane == 0) __hip_atomic_store(&hs->seq, nx.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    h.r0 = px.r;
-    h.c0 = px.c;
-    h.v0 = o.v;
-    h.s0r = o.pr;
-    h.s0c = o.pc;
-    h.i0 = o.img;
-    h.n0 = o.nn;
+    if (px.r + 1 < g.bh && px.c >= 2)  // row r + 1 gathers (r + 1, c - 2) at step t + 1
+      handoff_publish(nx.hand + (int64_t)job * g.bh + px.r, o, nx, lane);
+    qhand_own(h, px.r, px.c, o);
 #if IA_PROBE & 8
     __builtin_amdgcn_s_waitcnt(0);
     gs[1] = __builtin_amdgcn_s_memtime();
@@ -625,16 +622,7 @@ __device__ __forceinline__ void merge_gather_body(const LevelGeo &g, const StepD
   const QPix pn = ia_qpix(nx.sn, g.bw, mn);
   if (pn.r >= 1 && pn.c + 2 < g.bw) {  // (r - 1, c + 2) of step t: the row above's handoff
     const HandSlot *hs = nx.hand + (int64_t)job * g.bh + (pn.r - 1);
-    const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-    // relaxed: the slot is uncached (nothing stale to invalidate); its fields load after the
-    // seq was seen
-    while (__hip_atomic_load(&hs->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != nx.seq) {
-      if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > nx.timeout_ticks) {
-        atomicOr(nx.err, 16u);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
+    handoff_wait(hs, nx);
     h.r1 = pn.r - 1;
     h.c1 = pn.c + 2;
     h.v1 = hs->v;
