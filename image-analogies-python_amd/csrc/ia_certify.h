@@ -6,7 +6,7 @@
 
 // the certified single-rank winner of query m (exact NN over this rank's shard); RPL records per
 // lane (nwg <= 64 RPL).  dsc: dist() * dsc is in the units of the scan's values (the prescaled
-// index, ia_capi.cpp ia_index_build; 1 on the level path)
+// index, ia_index.cpp ia_index_build; 1 on the level path)
 template <int RPL = IA_WG_TARGET / IA_WAVE, class DistFn>
 __device__ Winner certified_winner(const MergeArgs &a, int m, DistFn &&dist, unsigned *stat_out, double dsc = 1.0) {
   const int lane = threadIdx.x & 63;

@@ -247,7 +247,7 @@ __global__ void __launch_bounds__(IA_WG) k_fill_random_f16(_Float16 *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launchers (called from ia_capi.cpp)
+// host-side launchers (called from ia_index.cpp)
 // ------------------------------------------------------------------------------------------
 void ia_launch_reduce_stats(const unsigned *pstat, int64_t n, unsigned long long *counters, hipStream_t st) {
   const int64_t nwg = std::min<int64_t>(256, std::max<int64_t>(1, cdiv(n, (int64_t)IA_WG * 16)));

@@ -1,0 +1,209 @@
+// ia_host.h — what every host unit of libia.so shares: error plumbing (fail, HIP_TRY, NCCL_TRY),
+// the owning device buffer, the context and index structs behind include/ia.h's opaque
+// pointers, and the few functions one unit needs from another.  Everything here is internal:
+// namespace ia_host and the two structs are hidden from the dynamic symbol table.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/ia.h"
+#include "ia_internal.h"
+#include "ia_launch.h"
+
+typedef struct ncclComm *ncclComm_t;  // as rccl.h has it; only ia_comm.cpp and the step loop include that
+
+namespace ia_host __attribute__((visibility("hidden"))) {
+
+// records msg as the calling thread's last error (ia_last_error) and returns code; ia_ctx.cpp
+int fail(int code, const std::string &msg);
+
+#define HIP_TRY(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess)                                                                      \
+      return fail(IA_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
+  } while (0)
+#define NCCL_TRY(expr)                                                                         \
+  do {                                                                                         \
+    ncclResult_t r_ = (expr);                                                                  \
+    if (r_ != ncclSuccess) return fail(IA_ECOMM, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
+  } while (0)
+
+// grow-only device buffer; owns its memory (freed with its holder: the device of that memory
+// must be current then, which ia_destroy / ia_index_destroy see to)
+struct DevBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  int ensure(size_t bytes) {
+    if (bytes <= cap) return IA_OK;
+    release();
+    size_t want = std::max<size_t>(bytes, 256);
+    if (hipMalloc(&p, want) != hipSuccess) {
+      p = nullptr;  // (the destructor frees p)
+      return fail(IA_ENOMEM, "hipMalloc of " + std::to_string(want) + " bytes failed");
+    }
+    cap = want;
+    return IA_OK;
+  }
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <class T>
+  T *as() const {
+    return reinterpret_cast<T *>(p);
+  }
+};
+
+struct JobBufs {  // moved, never copied, when ia_ctx::jb grows (earlier jobs' buffers stay live)
+  DevBuf B, Bc, Bpc, Bp, S, IM, W, DSRC, DDIST, pstat, NN;
+};
+
+inline int kh_for(int d_plus_norm) {  // smallest instantiated K3 width that holds d + norm column
+  if (d_plus_norm <= 56) return 28;
+  if (d_plus_norm <= 112) return 56;
+  if (d_plus_norm <= 168) return 84;
+  return -1;
+}
+
+// device-side waits (handoffs, exchange flags) give up after 20 s of the 100 MHz s_memrealtime clock
+static constexpr long long IA_WAIT_TICKS = 2000000000LL;
+
+static inline int64_t tile_pad(int64_t n) { return (n + IA_TILE - 1) / IA_TILE * IA_TILE; }
+
+// a level's share of the process-wide budget of handoff-chained waves (ia_ctx.cpp g_chain_waves),
+// returned when the level call ends
+struct ChainReservation {
+  int n = 0;
+  ~ChainReservation();
+  bool take(int w, int budget);
+};
+int chain_waves_in_flight();
+
+// ia_comm.cpp
+int xchg_alloc(ia_ctx *c, int world, bool fresh = false);
+void comm_close(ia_ctx *c);  // the communicator and the peers' IPC mappings (ia_destroy)
+bool shard_level(int64_t n_tiles, int world);
+
+}  // namespace ia_host
+
+using ia_host::DevBuf;
+using ia_host::JobBufs;
+
+struct __attribute__((visibility("hidden"))) ia_ctx {
+  int dev = 0;
+  hipStream_t st = nullptr;
+  // uploads (IA_MEM_HOST) and per-level scratch
+  DevBuf A, Ac, Ap, Apc;
+  std::vector<JobBufs> jb;  // per job of a batch: B-side uploads / outputs, stats words
+  DevBuf jobs;              // device JobPtrs[n_jobs]
+  DevBuf db, db64, mu, Rbits, q64, qn2, qf, rec, recT, win, allwin, counters, absmax;
+  // certified pruned scan (option "prune"): per-level basis, sorted DB table, tile boxes
+  DevBuf pr_part, pr_cov, pr_basis, pr_proj, pr_keys, pr_rows, pr_tmp, pos2row, boxes, qinfo, pairs;
+  DevBuf qs_order, qs_info, qs_frag, qs_tbox;  // presorted queries of a step (K2s, or the fused gathers' sort)
+  DevBuf tnorm;  // per DB tile of a pruned level: R_t >= max |a'| over its rows
+  DevBuf py_in, py_tmp, py_sm, py_mm, py_out;  // GPU preprocessing (ia_gaussian_pyramid, ia_color_matrix)
+  std::vector<double> basis_h;   // staging of the basis upload (lives until the copy ran)
+  int64_t prune_min_rows = IA_PRUNE_MIN_ROWS;  // option "prune_min_rows": smallest DB that prunes
+  int prune = 1;
+  int row_source = 0;            // option "row_source": exact rows from 0 = the fp64 row DB (1 = the A images,
+                                 // measured slower, is in git history only)
+  int shard_emulate = 1;         // option "shard_emulate": W > 1 runs a W-way DB shard on this device
+  int shard_unpruned = 0;        // option "shard_unpruned": 1 = shard levels that scan unpruned too
+  int prune_group = 1;           // option "prune_group": Morton tiles interleaved in groups of G (ia_prune.hip k_make_table)
+  int matcher = IA_MATCH_F16X3;  // option "matcher"
+  int k3p_variant = 24;          // option "k3p_variant": pruned-scan kernel version (ia_k3h.hip k3h_prune*),
+                                 // 24 / 25 two passes (a hi stream three tiles deep, then
+                                 // the passing tiles' chains); 22 hi-only stream with the chains one tile later;
+                                 // 20 / 21 whole tiles, corrections fused on query-tile pairs.  In-kernel sort up
+                                 // to 512 queries (20, 22, 24), presorted above (21, 25); the other versions are
+                                 // in git history
+  int k3_variant = 1;            // option "k3_variant": K3h epilogue (1 = packed index, the only one built)
+  int k3p_blocks = 1;            // option "k3p_blocks": 1 = a wide step's presorted pruned scan is one launch over
+                                 // all its query blocks (2-D grid); 0 = one launch per block
+  int fuse_gather = 1;           // option "fuse_gather": 1 = K4 of step t and K2p of step t + 1 in one launch
+  int fuse_unpruned = 0;         // option "fuse_unpruned": 1 = also on unpruned levels (K4 + K2h)
+  HandSlot *hand = nullptr;      // its per-row handoff slots (uncached)
+  int hand_rows = 0;
+  int prefetch_next = 1;         // option "prefetch_next" (NextStep::prefetch)
+  int early_gather = 1;          // option "early_gather" (NextStep::early)
+  int gather_wave = 1;           // option "gather_wave" (NextStep::gwave): the early path on two-wave workgroups
+  int nn_bound = 1;              // option "nn_bound" (JobPtrs::nn): the pruned one-rank levels' gathers also
+                                 // bound U' by the causal neighbours' exact NN rows, shifted
+  int fuse_sort = 0;             // option "fuse_sort": the fused gathers of step t + 1 also sort it (NextStep::kslot);
+                                 // 2 = on levels whose widest step has >= IA_FUSE_SORT_MINQ queries; off by
+                                 // default: no gain left with nn_bound
+  int chain_budget = 0;          // waves of handoff-chained launches this context's CUs hold deadlock-free
+  int scan_wgs = IA_NWG_H;       // option "scan_wgs": workgroups of a pruned scan launch (<= one per CU)
+                                 // (ia_init: 2 x the resident merge-gather waves - a margin; see g_chain_waves)
+  unsigned long long *kslot = nullptr;  // their per-query key slots (uncached)
+  int kslot_n = 0;
+  unsigned hseq = 0;
+  // per-step K3 timing (optional)
+  int time_dist = 0;
+  int stamps = 0;                 // option "stamps": per-launch device time from kernel stamps
+  int rec_wt = 1;                 // option "rec_wt": K3p records stored write-through
+  DevBuf stamp_k3, stamp_mg, stamp_dur;
+  std::vector<hipEvent_t> evs, evg, evm;  // sampled steps: K3, K2 and K4 brackets
+  hipEvent_t lv0 = nullptr, lv1 = nullptr, lv2 = nullptr;
+  hipEvent_t kb[4] = {nullptr, nullptr, nullptr, nullptr};  // per level: K1b start / end, K1 start / end
+  // multi-GPU
+  int rank = 0, world = 1;
+  ncclComm_t comm = nullptr;
+  int exchange = 0;               // option "exchange": 0 = RCCL all-gather + finish, 1 = peer-write merge,
+                                  // 2 = owner-computes (rank o owns job o; every rank scans its shard for all)
+  DevBuf xo_inv;                  // exchange = 2: the owners' query -> slot tables of the current step
+  int xo_presort = 0;             // option "xo_presort": 1 = owners always sort with K2s (tests)
+  int xo_wait = 0;                // option "xo_wait": 1 = the fused merge waits for every owner's next
+                                  // queries (one wave), so the next scan does not spin on all CUs
+  void *xbuf = nullptr;           // this process's exchange buffer (uncached, IPC-exportable)
+  int xbuf_w = 0;                 // ranks the buffer was sized for
+  XSlot *xpeer[IA_XCHG_MAXW] = {};  // every rank's buffer in this address space (ia_xchg_open)
+  bool xmapped[IA_XCHG_MAXW] = {};  // opened through hipIpcOpenMemHandle (closed on destroy)
+  unsigned xseq = 0;              // exchange sequence number (one per sharded step, same on every rank)
+  bool xfresh = false;            // the buffer was zeroed by ia_xchg_alloc and not opened since
+  DevBuf xerr;
+  // level pipelining: a recording context publishes, per level call (a
+  // generation), the wavefront steps it has enqueued, each followed by an event; a context told
+  // to depend on it (ia_pipeline_depend) makes each of its steps wait for the steps of that
+  // generation it reads from (level l + 1 step t reads B' of level l steps <= t / 2 + 4)
+  int p_record = 0;                          // option "pipeline_record"
+  int p_last = 0;                            // option "pipeline_last": the next level call has no
+                                             // dependents (no per-step events; one call only)
+  std::vector<hipEvent_t> p_ev[3];           // per generation mod 3: one event per step
+  std::atomic<long long> p_enq{-1};          // last step of the current generation enqueued
+  std::atomic<long long> p_T{0};             // steps of the current generation
+  std::atomic<int> p_gen{0}, p_done{0};      // current / last finished generation
+  ia_ctx *dep = nullptr;                     // the next level call waits on dep's generation dep_gen
+  int dep_gen = 0;
+};
+
+struct __attribute__((visibility("hidden"))) ia_index {
+  ia_ctx *ctx = nullptr;
+  int64_t n = 0;
+  int d = 0, KH = 0, n_tiles = 0, tpw = 0, nwg = 0;
+  double sc = 1.;             // power-of-two prescale of the centred fp32 copy (ia_dense.hip)
+  std::vector<double> mu_h;   // column means (the queries' range check)
+  DevBuf pts, db, mu, Rbits, q, q64, qn2, qf, rec, recT, idx, dist, counters;
+  DevBuf cpx, cs, cim, cout;  // ia_coherence_batch staging
+};

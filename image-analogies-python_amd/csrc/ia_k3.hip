@@ -149,7 +149,7 @@ k3_dist(const float4 *__restrict__ db, const float4 *__restrict__ qf, int n_tile
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launchers (called from ia_capi.cpp)
+// host-side launchers (called from ia_level_run.cpp, ia_index.cpp)
 // ------------------------------------------------------------------------------------------
 // K3 dispatch table: QT query tiles per launch (1..QTMAX(KH))
 typedef void (*k3_fn)(const float4 *, const float4 *, int, int, int, int, int, int, int, float4 *, float *);

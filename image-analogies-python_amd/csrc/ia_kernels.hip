@@ -669,7 +669,7 @@ k_merge_gather(LevelGeo g, StepDesc sd, Imgs A, MergeArgs ma, JS jobs, Imgs B, N
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launchers (called from ia_capi.cpp)
+// host-side launchers (called from ia_level_run.cpp)
 // ------------------------------------------------------------------------------------------
 void ia_launch_merge(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const MergeArgs &ma, Winner *win,
                      const JobSet &jobs, bool fused, hipStream_t st) {
@@ -727,7 +727,7 @@ void ia_launch_merge_gather(const LevelGeo &g, const StepDesc &sd, const Imgs &A
     return;
   }
 }
-// the chained-wave budget's inputs (ia_capi.cpp, ia_chain_budget): the most VGPRs per lane over
+// the chained-wave budget's inputs (ia_ctx.cpp, ia_chain_budget): the most VGPRs per lane over
 // every k_merge_gather instance the library launches, and the workgroups per CU the occupancy
 // API admits and the workgroup size of the instance with the fewest resident waves per CU, from
 // the compiled kernels themselves

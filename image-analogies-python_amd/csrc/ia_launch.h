@@ -1,6 +1,6 @@
 // ia_launch.h — host launchers of the kernels in ia_level_db.hip, ia_gather.hip, ia_k3.hip,
 // ia_kernels.hip (the per-step merges), ia_merge_shard.hip, ia_dense.hip, ia_prune.hip,
-// ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by ia_capi.cpp.
+// ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -246,10 +246,10 @@ __global__ void __launch_bounds__(IA_WG) k_db_build_h(LevelGeo g, const double *
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launchers (called from ia_capi.cpp)
+// host-side launchers (called from ia_level_plan.cpp)
 // ------------------------------------------------------------------------------------------
 void ia_launch_means(int ch, const Imgs &A, int n_ap, double *mu, hipStream_t st) {
-  // partial sums live behind the 4 CH means in the same buffer (ia_capi.cpp sizes it)
+  // partial sums live behind the 4 CH means in the same buffer (ia_level_plan.cpp sizes it)
   double *parts = mu + 16;
   with_ch(ch, [&](auto c) {
     constexpr int CH = decltype(c)::CH;

@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(IA_PQ_WG) k_merge_xchg(LevelGeo g, StepDesc sd
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launchers (called from ia_capi.cpp)
+// host-side launchers (called from ia_level_run.cpp)
 // ------------------------------------------------------------------------------------------
 void ia_launch_finish(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const double *db64, const double *q64,
                       const Winner *allwin, int world, int Mstride, const JobSet &jobs, hipStream_t st) {

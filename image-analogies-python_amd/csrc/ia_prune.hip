@@ -5,7 +5,7 @@
 // of R^D, sum_i (u_i . (a - q))^2 <= |a - q|^2, so a row whose projection box lies further than
 // sqrt(U) from q's projection can be skipped without changing the result.  Per level:
 //   K5a/K5b  covariance of the centred fp64 DB rows (sampled, deterministic two-pass reduction);
-//            the host takes its top IA_NPC eigenvectors (Jacobi, ia_capi.cpp) as the basis
+//            the host takes its top IA_NPC eigenvectors (Jacobi, ia_level_plan.cpp) as the basis
 //   K5c      projections of every row onto the basis + a Morton key of the quantised
 //            projections; hipCUB radix sort of (key, row) orders the DB so that 32-row tiles
 //            are compact in projection space

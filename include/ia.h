@@ -207,7 +207,7 @@ int ia_version(void);
  * either way; no faster since option nn_bound.
  * Fused merge + gather launches (option "fuse_gather") wait row to row; a level uses them only
  * while the chained waves of all levels in flight in the process stay under twice the GPU's
- * resident k_merge_gather waves (else it runs separate launches; ia_capi.cpp g_chain_waves).
+ * resident k_merge_gather waves (else it runs separate launches; ia_ctx.cpp g_chain_waves).
  * "rec_wt" = 1 (default) / 0: the pruned scan stores its per-(query, chunk) records write-through
  * (sc1 buffer stores), so the scan -> merge kernel boundary has no dirty record lines to write
  * back (one-rank steps; the owner-computes exchange has its own uncached stores).  Exact either

@@ -28,7 +28,7 @@ REL_TIE = 2.0 ** -20      # tests/adversarial_inputs.py REL_TIE
 # ---- the exact index ---------------------------------------------------------------------------
 def index_geometry(n, d=55):
     """(n_tiles, tpw, nwg, tiles of the last chunk, rows of the last tile, KH, query tiles of one scan launch) of
-    ia_index_build / ia_index_query (ia_capi.cpp), restated"""
+    ia_index_build / ia_index_query (ia_index.cpp), restated"""
     n_tiles = -(-n // TILE)
     tpw = max(4, -(-n_tiles // WG_TARGET))
     nwg = -(-n_tiles // tpw)

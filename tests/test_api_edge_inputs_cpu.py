@@ -1,5 +1,5 @@
 """Each case of tests/api_edge_inputs.py is what it claims to be: it reaches the code path it is
-named for (the launch geometry restated from ia_capi.cpp / ia_pyramid.hip) and the reference's own
+named for (the launch geometry restated from ia_index.cpp / ia_pyramid.hip) and the reference's own
 answer on it has the property the GPU test relies on.  No GPU.
 
 These are conditions on the inputs, not measurements: a generator that misses one is changed (or

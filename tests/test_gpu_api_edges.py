@@ -1,5 +1,5 @@
 """GPU parity of the C ABI off the level path on the cases of tests/api_edge_inputs.py:
-ia_index_build / ia_index_query (ia_capi.cpp, ia_dense.hip, certified_winner), ia_coherence_batch
+ia_index_build / ia_index_query (ia_index.cpp, ia_dense.hip, certified_winner), ia_coherence_batch
 (k_coherence_batch), ia_gaussian_pyramid / ia_color_matrix (ia_pyramid.hip).  Each test names the
 code path it executes and why its size reaches it; tests/test_api_edge_inputs_cpu.py pins that on
 the CPU.  Every comparison is bit for bit with a plain fp64 reference (numpy, the oracle, the

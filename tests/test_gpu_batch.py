@@ -262,7 +262,7 @@ def test_cfg5_pruned_batches_fit_the_chain_budget(ctx):
     16 x 171 = 2,736 queries in a step, and three contexts run such levels at once.  Fused
     merge + gather launches that many waves wide could stall on each other's row handoffs (every
     resident slot held by a wave whose predecessor row is not dispatched); the process-wide
-    chained-wave budget (ia_capi.cpp g_chain_waves) makes those levels run separate launches.
+    chained-wave budget (ia_ctx.cpp g_chain_waves) makes those levels run separate launches.
     The run must finish and equal the unpruned batched run bit for bit."""
     from ia_amd import _native, sweep, synth
     n = synth.CONFIGS['cfg5'][0]['size']

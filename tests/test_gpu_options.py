@@ -277,7 +277,7 @@ STAMP_FIELDS = ('k3p_stamp_ms', 'k3p_stamp_launches', 'merge_stamp_ms', 'merge_s
 
 def _check_stamps(sts):
     """The per-launch identities of include/ia.h on every level's own Stats (one job, one stream,
-    k3p_variant 24, steps of <= 352 queries).  ia_capi.cpp launches one pruned scan and one merge
+    k3p_variant 24, steps of <= 352 queries).  ia_level_run.cpp launches one pruned scan and one merge
     (fused or separate) per wavefront step on the context's stream, so k3p_stamp_launches ==
     dist_launches and merge_stamp_launches == steps; kernels of one stream do not overlap, so
     neither kind's summed device time can exceed the level's window (first scan start -> last
