@@ -102,6 +102,9 @@ EXPORTS = {
                                       ctypes.POINTER(ctypes.c_void_p)]),
     'ia_index_query': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                       ctypes.c_void_p]),
+    'ia_index_query_knn': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
+    'ia_index_knn_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'ia_index_destroy': (None, [ctypes.c_void_p]),
     'ia_coherence_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
@@ -366,8 +369,11 @@ class Context(object):
         return st
 
 
+KNN_MAX = 64  # IA_KNN_MAX of include/ia.h
+
+
 class ExactIndex(object):
-    """ia_index_*: exact 1-NN over fp64 rows (FLANN `linear` semantics, numpy summation order)."""
+    """ia_index_*: exact 1-NN and k-NN over fp64 rows (FLANN `linear` semantics, numpy summation order)."""
 
     def __init__(self, ctx, pts):
         pts = _c64(pts)
@@ -386,6 +392,25 @@ class ExactIndex(object):
         dist = np.empty(q.shape[0], dtype=np.float64)
         check(lib().ia_index_query(self._h, _ptr(q), q.shape[0], _ptr(idx), _ptr(dist)), 'ia_index_query')
         return idx, dist
+
+    def query_knn(self, q, k):
+        """ia_index_query_knn: the k nearest rows of every query, ascending (distance, index), lowest
+        index on ties; 1 <= k <= min(n, KNN_MAX).  Returns (idx (nq, k) int64, dist (nq, k) float64)."""
+        q = _c64(np.atleast_2d(q))
+        if q.shape[1] != self.d:
+            raise IAError('ExactIndex.query_knn: query width %d != index width %d' % (q.shape[1], self.d))
+        k = int(k)
+        idx = np.empty((q.shape[0], max(k, 0)), dtype=np.int64)
+        dist = np.empty((q.shape[0], max(k, 0)), dtype=np.float64)
+        check(lib().ia_index_query_knn(self._h, _ptr(q), q.shape[0], k, _ptr(idx), _ptr(dist)), 'ia_index_query_knn')
+        return idx, dist
+
+    def knn_stats(self):
+        """ia_index_knn_stats of the last query_knn: (rows whose exact fp64 distance was computed,
+        scan chunks rescanned exactly)."""
+        out = (ctypes.c_int64 * 2)()
+        check(lib().ia_index_knn_stats(self._h, out), 'ia_index_knn_stats')
+        return int(out[0]), int(out[1])
 
     def coherence(self, q, px, s, im, A_hw, Bp_w, pad=2):
         """ia_coherence_batch: best_coherence_match (algorithms.py:92-130) of every pixel px[i]

@@ -70,7 +70,8 @@ def compute_feature_array(im_pyr, c, full_feat):
 
 class GpuFLANN(object):
     """Duck-typed pyflann.FLANN (algorithms.py:56): build_index(pts, algorithm=...) returns a
-    params dict with 'checks'; nn_index(q, 1, checks=...) returns (indices, squared distances).
+    params dict with 'checks'; nn_index(q, 1, checks=...) returns (indices, squared distances),
+    1-D for num_neighbors = 1 and (nq, k) for k = 2..min(n, 64), nearest first.
     Backed by libia's exact GPU index; `algorithm` / `checks` are accepted and recorded."""
 
     def __init__(self, ctx=None):
@@ -85,10 +86,12 @@ class GpuFLANN(object):
     def nn_index(self, qpts, num_neighbors=1, checks=None, **kwargs):
         if self._index is None:
             raise _native.IAError('nn_index called before build_index')
-        if num_neighbors != 1:
-            raise _native.IAError('GpuFLANN.nn_index: only num_neighbors=1 is supported')
-        idx, dist = self._index.query(np.atleast_2d(qpts))
-        return idx, dist
+        kmax = min(self._index.n, _native.KNN_MAX)
+        if not 1 <= num_neighbors <= kmax:
+            raise _native.IAError('GpuFLANN.nn_index: num_neighbors must be 1..%d (got %r)' % (kmax, num_neighbors))
+        if num_neighbors == 1:
+            return self._index.query(np.atleast_2d(qpts))
+        return self._index.query_knn(np.atleast_2d(qpts), num_neighbors)   # (nq, k) arrays, as pyflann
 
     def delete_index(self):
         if self._index is not None:

@@ -3,6 +3,7 @@
 // their launchers.
 #include "ia_certify.h"
 #include "ia_launch.h"
+#include "ia_topk.h"
 
 // option "stamps": launch i's first workgroup start and last workgroup end over its `stride`
 // workgroup slots (unwritten slots are zero), in s_memrealtime ticks; one wave per launch
@@ -167,6 +168,39 @@ __global__ void __launch_bounds__(IA_WG) k_merge_dense(MergeArgs ma, const doubl
   }
 }
 
+// exact k-NN of the index (ia_index_query_knn): the certified k nearest rows of each query,
+// ascending (distance, row), from the same scan records as k_merge_dense.  counters[0] += rows
+// whose exact distance was computed, counters[1] += chunks rescanned (ia_index_knn_stats).
+__global__ void __launch_bounds__(IA_WG) k_merge_dense_knn(MergeArgs ma, const double *__restrict__ pts, int d,
+                                                            const double *__restrict__ q, int64_t nq, int k, double dsc,
+                                                            int64_t *__restrict__ idx_out, double *__restrict__ dist_out,
+                                                            unsigned long long *__restrict__ counters) {
+  const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
+  if (m >= nq) return;
+  const int lane = threadIdx.x & 63;
+  const double *qm = q + (int64_t)m * d;
+  double md;
+  int64_t mi;
+  unsigned long long n_exact, n_rescan;
+  certified_topk(ma, m, k, [&](int64_t row) {
+    const double *a = pts + row * d;
+    return pw_sum_rt([&](int f) {
+      const double x = a[f] - qm[f];
+      return x * x;
+    }, d);
+  }, dsc, md, mi, n_exact, n_rescan);
+  if (lane < k) {
+    idx_out[(int64_t)m * k + lane] = mi;
+    dist_out[(int64_t)m * k + lane] = md;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n_exact += __shfl_xor(n_exact, o, 64);
+  if (lane == 0) {  // integer sums: order-free
+    atomicAdd(&counters[0], n_exact);
+    if (n_rescan) atomicAdd(&counters[1], n_rescan);
+  }
+}
+
 // best_coherence_match (algorithms.py:92-130) for a batch of B' pixels against an index's rows,
 // one wave per pixel.  Lane j < (pad+1)(2 pad+1) is the window cell (row - pad + j / (2 pad+1),
 // col - pad + j % (2 pad+1)), i.e. product(rows, cols) order (:101-104); a cell is a candidate
@@ -271,6 +305,11 @@ void ia_launch_dense_query(int KH, const double *q, int64_t nq, int d, int Mpad,
 void ia_launch_merge_dense(const MergeArgs &ma, const double *pts, int d, const double *q, int64_t nq, double dsc,
                            int64_t *idx, double *dist, hipStream_t st) {
   hipLaunchKernelGGL(k_merge_dense, dim3(cdiv(nq, IA_WG / IA_WAVE)), dim3(IA_WG), 0, st, ma, pts, d, q, nq, dsc, idx, dist);
+}
+void ia_launch_merge_dense_knn(const MergeArgs &ma, const double *pts, int d, const double *q, int64_t nq, int k, double dsc,
+                               int64_t *idx, double *dist, unsigned long long *counters, hipStream_t st) {
+  hipLaunchKernelGGL(k_merge_dense_knn, dim3(cdiv(nq, IA_WG / IA_WAVE)), dim3(IA_WG), 0, st, ma, pts, d, q, nq, k, dsc, idx,
+                     dist, counters);
 }
 void ia_launch_coherence_batch(const double *pts, int64_t n, int d, const double *q, int64_t nq, const int32_t *px,
                                const int32_t *s, const int32_t *im, int64_t n_s, int a_h, int a_w, int bp_w, int pad,

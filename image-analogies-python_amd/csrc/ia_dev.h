@@ -18,7 +18,8 @@
 //
 // Here: feature geometry and access, numpy's and OpenBLAS's summation orders, the wave
 // reductions, the exact row distances and the certification bounds; at the end the two host
-// helpers every launcher dispatches through.  ia_certify.h and ia_gather.h build on it.
+// helpers every launcher dispatches through.  ia_certify.h, ia_topk.h (the index's certified
+// k-NN list) and ia_gather.h build on it.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (no FMA contraction: the exact
 // fp64 paths must round exactly like numpy's separate multiply and add).

@@ -204,6 +204,7 @@ struct __attribute__((visibility("hidden"))) ia_index {
   int d = 0, KH = 0, n_tiles = 0, tpw = 0, nwg = 0;
   double sc = 1.;             // power-of-two prescale of the centred fp32 copy (ia_dense.hip)
   std::vector<double> mu_h;   // column means (the queries' range check)
-  DevBuf pts, db, mu, Rbits, q, q64, qn2, qf, rec, recT, idx, dist, counters;
+  DevBuf pts, db, mu, Rbits, q, q64, qn2, qf, rec, recT, idx, dist, counters;  // idx / dist: batch x k results
   DevBuf cpx, cs, cim, cout;  // ia_coherence_batch staging
+  unsigned long long knn_stats[2] = {0, 0};  // the last ia_index_query_knn call: exact rows, chunks rescanned
 };

@@ -35,6 +35,9 @@ void ia_launch_dense_query(int KH, const double *q, int64_t nq, int d, int Mpad,
                            float *qf, hipStream_t st);
 void ia_launch_merge_dense(const MergeArgs &ma, const double *pts, int d, const double *q, int64_t nq, double dsc,
                            int64_t *idx, double *dist, hipStream_t st);
+// exact k-NN merge of the index (1 <= k <= 64): idx / dist are nq x k; counters[0..1] accumulate
+void ia_launch_merge_dense_knn(const MergeArgs &ma, const double *pts, int d, const double *q, int64_t nq, int k, double dsc,
+                               int64_t *idx, double *dist, unsigned long long *counters, hipStream_t st);
 void ia_launch_coherence_batch(const double *pts, int64_t n, int d, const double *q, int64_t nq, const int32_t *px,
                                const int32_t *s, const int32_t *im, int64_t n_s, int a_h, int a_w, int bp_w, int pad,
                                int32_t *p_out, int32_t *img_out, int32_t *r_out, unsigned *err, hipStream_t st);

@@ -5,10 +5,12 @@ three call sites: `pf.FLANN()` (algorithms.py:56), `build_index(pts, algorithm='
 (:69, returns a params dict with 'checks') and `nn_index(q, 1, checks=...)` (:74, returns
 (indices, squared distances)).  A maintainer who keeps the reference's per-pixel loop replaces
 that import with `import flann_mi355x as pf`.  Only the C ABI of include/ia.h is used here
-(ctypes, no torch): ia_init, ia_index_build, ia_index_query, ia_index_destroy, ia_last_error.
+(ctypes, no torch): ia_init, ia_index_build, ia_index_query, ia_index_query_knn, ia_index_destroy,
+ia_last_error.
 
-Semantics change from FLANN's randomised kd-forest to exact 1-NN: squared L2 in fp64 with
+Semantics change from FLANN's randomised kd-forest to exact k-NN: squared L2 in fp64 with
 numpy's summation order, lowest index on ties (FLANN `linear`, the reference's brute force).
+num_neighbors = 1 returns 1-D arrays, 2..min(n, 64) returns (nq, k) arrays, nearest first.
 """
 import ctypes
 import os
@@ -19,6 +21,7 @@ _LIB = os.environ.get('IA_LIBIA', os.path.join(os.path.dirname(os.path.abspath(_
 _vp, _i64 = ctypes.c_void_p, ctypes.c_int64
 _L = None
 _ctx = None
+KNN_MAX = 64   # IA_KNN_MAX
 
 
 def _lib():
@@ -28,6 +31,7 @@ def _lib():
         L.ia_init.argtypes = [ctypes.c_int, ctypes.POINTER(_vp)]
         L.ia_index_build.argtypes = [_vp, _vp, _i64, ctypes.c_int, ctypes.POINTER(_vp)]
         L.ia_index_query.argtypes = [_vp, _vp, _i64, _vp, _vp]
+        L.ia_index_query_knn.argtypes = [_vp, _vp, _i64, ctypes.c_int, _vp, _vp]
         L.ia_index_destroy.argtypes = [_vp]
         L.ia_index_destroy.restype = None
         L.ia_last_error.restype = ctypes.c_char_p
@@ -59,14 +63,27 @@ class FLANN(object):
     def nn_index(self, qpts, num_neighbors=1, checks=32, **kw):
         if self._h is None:
             raise RuntimeError('nn_index called before build_index')
-        if num_neighbors != 1:
-            raise ValueError('flann_mi355x: only num_neighbors=1 is supported')
+        kmax = min(len(self._pts), KNN_MAX)
+        if not 1 <= num_neighbors <= kmax:
+            raise ValueError('flann_mi355x: num_neighbors must be 1..%d (got %r)' % (kmax, num_neighbors))
         q = np.ascontiguousarray(np.atleast_2d(qpts), dtype=np.float64)
-        idx = np.empty(len(q), np.int64)
-        dist = np.empty(len(q), np.float64)
-        if _lib().ia_index_query(self._h, q.ctypes.data, len(q), idx.ctypes.data, dist.ctypes.data):
+        if num_neighbors == 1:
+            idx = np.empty(len(q), np.int64)
+            dist = np.empty(len(q), np.float64)
+            rc = _lib().ia_index_query(self._h, q.ctypes.data, len(q), idx.ctypes.data, dist.ctypes.data)
+        else:
+            k = int(num_neighbors)
+            idx = np.empty((len(q), k), np.int64)
+            dist = np.empty((len(q), k), np.float64)
+            rc = _lib().ia_index_query_knn(self._h, q.ctypes.data, len(q), k, idx.ctypes.data, dist.ctypes.data)
+        if rc:
             raise RuntimeError(_lib().ia_last_error().decode())
         return idx, dist
+
+    def nn(self, pts, qpts, num_neighbors=1, **kw):
+        """pyflann's one-shot form: build_index(pts), then nn_index(qpts, num_neighbors)"""
+        self.build_index(pts, **kw)
+        return self.nn_index(qpts, num_neighbors, **kw)
 
     def delete_index(self):
         if self._h is not None:

@@ -305,6 +305,21 @@ int ia_index_build(ia_ctx *ctx, const double *pts, int64_t n, int d, ia_index **
  * IA_EINVAL (nothing written) when a query value is not finite or lies farther from its column's
  * mean than 2^100 times the largest such distance of any row value. */
 int ia_index_query(ia_index *index, const double *q, int64_t nq, int64_t *idx_out, double *dist_out);
+/* nn_index(q, k): exact k-NN under the same distance.  Row j of idx_out (nq x k int64) and dist_out
+ * (nq x k fp64, may be NULL) holds the k rows with the smallest (distance, row index) pairs in
+ * ascending (distance, index) order: ties, also across the k-th place, go to the lower index.
+ * k = 1 returns what ia_index_query returns, bit for bit.  1 <= k <= min(n, IA_KNN_MAX); the
+ * merge keeps one list entry per lane of a wave, so 64 is the design's limit, not a tunable.
+ * IA_EINVAL (nothing written) for k outside that range, a NULL index / q / idx_out, nq < 0 (all
+ * checked before any GPU call) and for a query ia_index_query refuses.  The scan is
+ * ia_index_query's; only rows its records cannot rule out are computed in fp64. */
+#define IA_KNN_MAX 64
+int ia_index_query_knn(ia_index *index, const double *q, int64_t nq, int k, int64_t *idx_out,
+                       double *dist_out);
+/* Work of the last ia_index_query_knn call that ran on this index: out[0] = rows whose exact fp64
+ * distance was computed (reranked candidates + rows of rescanned chunks; a brute force computes
+ * nq x n), out[1] = scan chunks rescanned exactly. */
+int ia_index_knn_stats(const ia_index *index, int64_t out[2]);
 void ia_index_destroy(ia_index *index);
 /* best_coherence_match (algorithms.py:92-130) for nq B' pixels against the index's rows (the
  * As of create_index, algorithms.py:63-67), one call per batch instead of one per pixel.
