@@ -105,6 +105,12 @@ EXPORTS = {
     'ia_index_query_knn': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_void_p]),
     'ia_index_knn_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'ia_index_count_radius': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
+    'ia_index_query_radius': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ia_index_set_workspace': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    'ia_index_radius_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'ia_index_destroy': (None, [ctypes.c_void_p]),
     'ia_coherence_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
@@ -373,7 +379,8 @@ KNN_MAX = 64  # IA_KNN_MAX of include/ia.h
 
 
 class ExactIndex(object):
-    """ia_index_*: exact 1-NN and k-NN over fp64 rows (FLANN `linear` semantics, numpy summation order)."""
+    """ia_index_*: exact 1-NN, k-NN and fixed-radius search over fp64 rows (FLANN `linear` semantics, numpy
+    summation order)."""
 
     def __init__(self, ctx, pts):
         pts = _c64(pts)
@@ -411,6 +418,61 @@ class ExactIndex(object):
         out = (ctypes.c_int64 * 2)()
         check(lib().ia_index_knn_stats(self._h, out), 'ia_index_knn_stats')
         return int(out[0]), int(out[1])
+
+    def _radius_args(self, what, q, radius):
+        q = _c64(np.atleast_2d(q))
+        if q.shape[1] != self.d:
+            raise IAError('ExactIndex.%s: query width %d != index width %d' % (what, q.shape[1], self.d))
+        r = np.asarray(radius, dtype=np.float64)
+        if r.ndim == 0:
+            r = np.full(q.shape[0], float(r))
+        r = np.ascontiguousarray(r)
+        if r.shape != (q.shape[0],):
+            raise IAError('ExactIndex.%s: radius must be a scalar or one value per query' % what)
+        return q, r
+
+    def count_radius(self, q, radius):
+        """ia_index_count_radius: per query the exact number of rows with squared distance < radius
+        (a scalar or one value per query), int64 (nq,)."""
+        q, r = self._radius_args('count_radius', q, radius)
+        count = np.empty(q.shape[0], dtype=np.int64)
+        check(lib().ia_index_count_radius(self._h, _ptr(q), q.shape[0], _ptr(r), _ptr(count)), 'ia_index_count_radius')
+        return count
+
+    def query_radius(self, q, radius, max_nn=None):
+        """ia_index_query_radius: the rows with squared distance < radius, nearest first, ties to the
+        lower index.  max_nn = None: the exact CSR form (offsets (nq + 1,), idx, dist), query j's rows at
+        offsets[j]:offsets[j + 1] (a counting call, then the query).  max_nn = m >= 1: (idx (nq, m),
+        dist (nq, m), count (nq,)) with the m nearest, padded with -1 / +inf; count is the full count."""
+        q, r = self._radius_args('query_radius', q, radius)
+        nq = q.shape[0]
+        if max_nn is None:
+            offsets = np.zeros(nq + 1, dtype=np.int64)
+            np.cumsum(self.count_radius(q, r), out=offsets[1:])
+        else:
+            if int(max_nn) < 1:
+                raise IAError('ExactIndex.query_radius: max_nn must be None or >= 1 (got %r)' % (max_nn,))
+            offsets = np.arange(nq + 1, dtype=np.int64) * int(max_nn)
+        idx = np.empty(int(offsets[-1]), dtype=np.int64)
+        dist = np.empty(int(offsets[-1]), dtype=np.float64)
+        count = np.empty(nq, dtype=np.int64)
+        check(lib().ia_index_query_radius(self._h, _ptr(q), nq, _ptr(r), _ptr(offsets), _ptr(idx), _ptr(dist),
+                                          _ptr(count)), 'ia_index_query_radius')
+        if max_nn is None:
+            return offsets, idx, dist
+        return idx.reshape(nq, int(max_nn)), dist.reshape(nq, int(max_nn)), count
+
+    def set_workspace(self, entries):
+        """ia_index_set_workspace: candidate entries a radius call keeps on the device per fill pass
+        (0: the default)."""
+        check(lib().ia_index_set_workspace(self._h, int(entries)), 'ia_index_set_workspace')
+
+    def radius_stats(self):
+        """ia_index_radius_stats of the last radius call: ((query, row) pairs verified in fp64, rows found
+        inside, fill sub-batches, query segments sorted outside LDS)."""
+        out = (ctypes.c_int64 * 4)()
+        check(lib().ia_index_radius_stats(self._h, out), 'ia_index_radius_stats')
+        return tuple(int(v) for v in out)
 
     def coherence(self, q, px, s, im, A_hw, Bp_w, pad=2):
         """ia_coherence_batch: best_coherence_match (algorithms.py:92-130) of every pixel px[i]

@@ -71,7 +71,8 @@ def compute_feature_array(im_pyr, c, full_feat):
 class GpuFLANN(object):
     """Duck-typed pyflann.FLANN (algorithms.py:56): build_index(pts, algorithm=...) returns a
     params dict with 'checks'; nn_index(q, 1, checks=...) returns (indices, squared distances),
-    1-D for num_neighbors = 1 and (nq, k) for k = 2..min(n, 64), nearest first.
+    1-D for num_neighbors = 1 and (nq, k) for k = 2..min(n, 64), nearest first; nn_radius(q, radius)
+    returns the rows inside a squared radius of one query.
     Backed by libia's exact GPU index; `algorithm` / `checks` are accepted and recorded."""
 
     def __init__(self, ctx=None):
@@ -92,6 +93,26 @@ class GpuFLANN(object):
         if num_neighbors == 1:
             return self._index.query(np.atleast_2d(qpts))
         return self._index.query_knn(np.atleast_2d(qpts), num_neighbors)   # (nq, k) arrays, as pyflann
+
+    def nn_radius(self, query, radius, max_nn=-1, **kwargs):
+        """pyflann's nn_radius: the rows within the squared distance `radius` of ONE query vector
+        (strictly: dist < radius), nearest first, as (indices int64, squared distances float64);
+        max_nn < 0: all of them, else the max_nn nearest.  sorted= / checks= are accepted and ignored
+        (the result is always sorted and exact)."""
+        if self._index is None:
+            raise _native.IAError('nn_radius called before build_index')
+        q = np.asarray(query, dtype=np.float64)
+        if q.size != self._index.d:
+            raise _native.IAError('GpuFLANN.nn_radius: one query vector of width %d expected' % self._index.d)
+        q = q.reshape(1, -1)
+        if max_nn < 0:
+            _, idx, dist = self._index.query_radius(q, float(radius))
+            return idx, dist
+        if max_nn == 0:
+            return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
+        idx, dist, count = self._index.query_radius(q, float(radius), int(max_nn))
+        cnt = min(int(count[0]), int(max_nn))
+        return idx[0, :cnt].copy(), dist[0, :cnt].copy()
 
     def delete_index(self):
         if self._index is not None:

@@ -15,6 +15,8 @@
 //   ia_merge_shard.hip  k_finish_level, k_merge_xchg: the merges of a sharded level
 //   ia_dense.hip        dense variants for the FLANN-compatible index (ia_index_*), statistics,
 //                       stamps, microbenchmark operands
+//   ia_k3r.hip          the index's fixed-radius search: K3's scan with a threshold epilogue (count
+//                       and fill passes), exact verification, per-query sort (ia_index_*_radius)
 //
 // Here: feature geometry and access, numpy's and OpenBLAS's summation orders, the wave
 // reductions, the exact row distances and the certification bounds; at the end the two host

@@ -207,4 +207,10 @@ struct __attribute__((visibility("hidden"))) ia_index {
   DevBuf pts, db, mu, Rbits, q, q64, qn2, qf, rec, recT, idx, dist, counters;  // idx / dist: batch x k results
   DevBuf cpx, cs, cim, cout;  // ia_coherence_batch staging
   unsigned long long knn_stats[2] = {0, 0};  // the last ia_index_query_knn call: exact rows, chunks rescanned
+  // fixed-radius search (ia_index_radius.cpp): per batch the radii, thresholds, per-(query, workgroup)
+  // counts and segments, per-query totals and offsets, result counts; per fill sub-batch the
+  // candidates (row, distance) and the staged results
+  DevBuf r_rad, r_thr, r_cnt, r_seg, r_ts, r_qoff, r_soff, r_cntq, r_wr, r_wd, r_sidx, r_sdist;
+  int64_t workspace = 0;                  // ia_index_set_workspace: candidate entries per fill pass (0: default)
+  int64_t radius_stats[4] = {0, 0, 0, 0};  // the last radius call (ia_index_radius_stats)
 };

@@ -1,5 +1,5 @@
 // ia_launch.h — host launchers of the kernels in ia_level_db.hip, ia_gather.hip, ia_k3.hip,
-// ia_kernels.hip (the per-step merges), ia_merge_shard.hip, ia_dense.hip, ia_prune.hip,
+// ia_kernels.hip (the per-step merges), ia_merge_shard.hip, ia_dense.hip, ia_k3r.hip, ia_prune.hip,
 // ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -38,6 +38,23 @@ void ia_launch_merge_dense(const MergeArgs &ma, const double *pts, int d, const 
 // exact k-NN merge of the index (1 <= k <= 64): idx / dist are nq x k; counters[0..1] accumulate
 void ia_launch_merge_dense_knn(const MergeArgs &ma, const double *pts, int d, const double *q, int64_t nq, int k, double dsc,
                                int64_t *idx, double *dist, unsigned long long *counters, hipStream_t st);
+// exact fixed-radius search of the index (ia_k3r.hip; sequence in ia_index_radius.cpp).  thr: (hi, lo)
+// per padded query; cnt / seg: one record per (query, scan workgroup); ts: (candidates, certain rows)
+// per query; qoff / soff: where a query's candidates / staged results start; [j0, j1): the queries of
+// a fill sub-batch
+void ia_launch_k3r_thresholds(const double *radius, const double *qn2, const unsigned *Rbits, int nq, int Mpad, double dsc,
+                              double eps_c, float2 *thr, hipStream_t st);
+void ia_launch_k3r_count(int KH, int qt, const float4 *db, const float4 *qf, const float2 *thr, int n_tiles, int tpw, int qt0,
+                         int M, int nwg, uint2 *cnt, hipStream_t st);
+void ia_launch_k3r_offsets(const uint2 *cnt, int nq, int nwg, bool count_only, uint2 *seg, uint2 *ts, hipStream_t st);
+void ia_launch_k3r_fill(int KH, int qt, bool count_only, const float4 *db, const float4 *qf, const float2 *thr, int n_tiles,
+                        int tpw, int qt0, int j0, int j1, int nwg, const uint2 *seg, const unsigned *qoff, int *cand,
+                        hipStream_t st);
+void ia_launch_k3r_verify(const double *pts, int64_t n, int d, int NT, const double *q, const double *radius, const uint2 *ts,
+                          const unsigned *qoff, int j0, int j1, unsigned max_len, int *wr, double *wd, hipStream_t st);
+void ia_launch_k3r_finish(bool count_only, const uint2 *ts, const unsigned *qoff, const unsigned *soff, int j0, int j1,
+                          int *wr, double *wd, int64_t *sidx, double *sdist, int64_t *cntq, hipStream_t st);
+int ia_k3r_sort_lds();  // longest segment k3r_finish sorts in LDS
 void ia_launch_coherence_batch(const double *pts, int64_t n, int d, const double *q, int64_t nq, const int32_t *px,
                                const int32_t *s, const int32_t *im, int64_t n_s, int a_h, int a_w, int bp_w, int pad,
                                int32_t *p_out, int32_t *img_out, int32_t *r_out, unsigned *err, hipStream_t st);

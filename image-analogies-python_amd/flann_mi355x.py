@@ -5,12 +5,13 @@ three call sites: `pf.FLANN()` (algorithms.py:56), `build_index(pts, algorithm='
 (:69, returns a params dict with 'checks') and `nn_index(q, 1, checks=...)` (:74, returns
 (indices, squared distances)).  A maintainer who keeps the reference's per-pixel loop replaces
 that import with `import flann_mi355x as pf`.  Only the C ABI of include/ia.h is used here
-(ctypes, no torch): ia_init, ia_index_build, ia_index_query, ia_index_query_knn, ia_index_destroy,
-ia_last_error.
+(ctypes, no torch): ia_init, ia_index_build, ia_index_query, ia_index_query_knn, ia_index_count_radius,
+ia_index_query_radius, ia_index_destroy, ia_last_error.
 
 Semantics change from FLANN's randomised kd-forest to exact k-NN: squared L2 in fp64 with
 numpy's summation order, lowest index on ties (FLANN `linear`, the reference's brute force).
 num_neighbors = 1 returns 1-D arrays, 2..min(n, 64) returns (nq, k) arrays, nearest first.
+nn_radius(query, radius) returns every row with squared distance < radius of one query, nearest first.
 """
 import ctypes
 import os
@@ -32,6 +33,8 @@ def _lib():
         L.ia_index_build.argtypes = [_vp, _vp, _i64, ctypes.c_int, ctypes.POINTER(_vp)]
         L.ia_index_query.argtypes = [_vp, _vp, _i64, _vp, _vp]
         L.ia_index_query_knn.argtypes = [_vp, _vp, _i64, ctypes.c_int, _vp, _vp]
+        L.ia_index_count_radius.argtypes = [_vp, _vp, _i64, _vp, _vp]
+        L.ia_index_query_radius.argtypes = [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]
         L.ia_index_destroy.argtypes = [_vp]
         L.ia_index_destroy.restype = None
         L.ia_last_error.restype = ctypes.c_char_p
@@ -79,6 +82,31 @@ class FLANN(object):
         if rc:
             raise RuntimeError(_lib().ia_last_error().decode())
         return idx, dist
+
+    def nn_radius(self, query, radius, max_nn=-1, **kw):
+        """pyflann's nn_radius: the rows with squared distance < radius of ONE query vector, nearest
+        first, as (indices int64, squared distances float64); max_nn < 0: all of them.  sorted= and
+        checks= are accepted and ignored."""
+        if self._h is None:
+            raise RuntimeError('nn_radius called before build_index')
+        q = np.ascontiguousarray(query, dtype=np.float64).reshape(1, -1)
+        if q.shape[1] != self._pts.shape[1]:
+            raise ValueError('flann_mi355x: one query vector of width %d expected' % self._pts.shape[1])
+        L = _lib()
+        r = np.array([radius], dtype=np.float64)
+        count = np.zeros(1, np.int64)
+        if max_nn < 0:   # the exact layout: count first
+            if L.ia_index_count_radius(self._h, q.ctypes.data, 1, r.ctypes.data, count.ctypes.data):
+                raise RuntimeError(L.ia_last_error().decode())
+        cap = int(count[0]) if max_nn < 0 else int(max_nn)
+        offsets = np.array([0, cap], dtype=np.int64)
+        idx = np.empty(max(cap, 1), np.int64)
+        dist = np.empty(max(cap, 1), np.float64)
+        if L.ia_index_query_radius(self._h, q.ctypes.data, 1, r.ctypes.data, offsets.ctypes.data, idx.ctypes.data,
+                                   dist.ctypes.data, count.ctypes.data):
+            raise RuntimeError(L.ia_last_error().decode())
+        cnt = min(int(count[0]), cap)
+        return idx[:cnt], dist[:cnt]
 
     def nn(self, pts, qpts, num_neighbors=1, **kw):
         """pyflann's one-shot form: build_index(pts), then nn_index(qpts, num_neighbors)"""

@@ -320,6 +320,36 @@ int ia_index_query_knn(ia_index *index, const double *q, int64_t nq, int k, int6
  * distance was computed (reranked candidates + rows of rescanned chunks; a brute force computes
  * nq x n), out[1] = scan chunks rescanned exactly. */
 int ia_index_knn_stats(const ia_index *index, int64_t out[2]);
+/* nn_radius(q, radius): exact fixed-radius search under the same distance (pyflann's radius is a
+ * squared distance too).  radius holds nq values, one per query, each >= 0 and not NaN; +inf means
+ * every row.  A row is inside when dist < radius, strictly: radius 0 returns nothing, even for an
+ * exact hit.  count_out[j] (required by both calls) is the exact number of rows inside query j's
+ * radius.
+ * The counting call returns only that; it verifies in fp64 just the rows whose fp32 scan value
+ * lies within the scan's error bound of the radius, every other row is decided by the scan.
+ * The query call writes rows as the caller lays them out: offsets holds nq + 1 non-decreasing
+ * values, offsets[0] >= 0, and query j owns slots [offsets[j], offsets[j + 1]) of idx_out (int64)
+ * and dist_out (fp64, may be NULL).  They receive the min(capacity, count) nearest rows inside the
+ * radius in ascending (distance, index) order, ties to the lower index; unused slots get index -1
+ * and distance +inf.  offsets[j] = j * max_nn is a fixed width; the running sum of a counting call's
+ * result is the exact CSR layout.
+ * IA_EINVAL with nothing written, checked before any GPU call, for a NULL index / q / radius /
+ * count_out / offsets, nq < 0, a negative or NaN radius, offsets that decrease or start below 0, a
+ * NULL idx_out with a non-empty layout, and a query the 1-NN call refuses. */
+int ia_index_count_radius(ia_index *index, const double *q, int64_t nq, const double *radius,
+                          int64_t *count_out);
+int ia_index_query_radius(ia_index *index, const double *q, int64_t nq, const double *radius,
+                          const int64_t *offsets, int64_t *idx_out, double *dist_out, int64_t *count_out);
+/* Caps the candidate entries (12 bytes each) a radius call keeps on the device per fill pass: a
+ * batch whose candidates exceed it is filled in sub-batches of consecutive queries.  0 restores
+ * the default, 2^23 entries.  Raised silently to the padded row count (n rounded up to 32), so one
+ * query always fits; the buffers grow to what a call needs, not to the cap. */
+int ia_index_set_workspace(ia_index *index, int64_t entries);
+/* Work of the last radius call (counting or query) that ran on this index: out[0] = (query, row)
+ * pairs whose exact fp64 distance was computed, out[1] = rows found inside their radius (the sum
+ * of count_out), out[2] = fill sub-batches, out[3] = query segments longer than 4,096 candidates,
+ * sorted in global memory instead of LDS. */
+int ia_index_radius_stats(const ia_index *index, int64_t out[4]);
 void ia_index_destroy(ia_index *index);
 /* best_coherence_match (algorithms.py:92-130) for nq B' pixels against the index's rows (the
  * As of create_index, algorithms.py:63-67), one call per batch instead of one per pixel.
