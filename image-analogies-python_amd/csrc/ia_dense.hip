@@ -155,13 +155,7 @@ __global__ void __launch_bounds__(IA_WG) k_merge_dense(MergeArgs ma, const doubl
   if (m >= nq) return;
   const double *qm = q + (int64_t)m * d;
   unsigned stat;
-  const Winner wn = certified_winner(ma, m, [&](int64_t row) {
-    const double *a = pts + row * d;
-    return pw_sum_rt([&](int f) {
-      const double x = a[f] - qm[f];
-      return x * x;
-    }, d);
-  }, &stat, dsc);
+  const Winner wn = certified_winner(ma, m, [&](int64_t row) { return row_dist2_rt(pts + row * d, qm, d); }, &stat, dsc);
   if ((threadIdx.x & 63) == 0) {
     idx_out[m] = wn.idx;
     dist_out[m] = wn.d;
@@ -182,13 +176,7 @@ __global__ void __launch_bounds__(IA_WG) k_merge_dense_knn(MergeArgs ma, const d
   double md;
   int64_t mi;
   unsigned long long n_exact, n_rescan;
-  certified_topk(ma, m, k, [&](int64_t row) {
-    const double *a = pts + row * d;
-    return pw_sum_rt([&](int f) {
-      const double x = a[f] - qm[f];
-      return x * x;
-    }, d);
-  }, dsc, md, mi, n_exact, n_rescan);
+  certified_topk(ma, m, k, [&](int64_t row) { return row_dist2_rt(pts + row * d, qm, d); }, dsc, md, mi, n_exact, n_rescan);
   if (lane < k) {
     idx_out[(int64_t)m * k + lane] = mi;
     dist_out[(int64_t)m * k + lane] = md;
@@ -241,13 +229,7 @@ __global__ void __launch_bounds__(IA_WG) k_coherence_batch(const double *__restr
   }
   double dist = INFINITY;
   int64_t key = ok ? lane : 64;
-  if (ok) {
-    const double *a = pts + dbrow * d, *qm = q + (int64_t)m * d;
-    dist = cr_sqrt(pw_sum_rt([&](int f) {
-      const double x = a[f] - qm[f];
-      return x * x;
-    }, d));
-  }
+  if (ok) dist = cr_sqrt(row_dist2_rt(pts + dbrow * d, q + (int64_t)m * d, d));
   if (e) atomicOr(err, e);
   wave_min_di(dist, key);  // first argmin (lowest window cell) among the candidates
   if (key >= 64) {

@@ -6,7 +6,8 @@
 //   ia_gather.hip       K2 k_gather_query / _h / _p: BBp_feat of every pixel of one wavefront
 //                       step (image_analogies.py:166-168, algorithms.py:78-89)
 //   ia_k3.hip           K3 k3_dist: best_approximate_match's distance scan (algorithms.py:73-75)
-//                       as a v_mfma_f32_32x32x2_f32 contraction with a fused per-query top-2
+//                       as a v_mfma_f32_32x32x2_f32 contraction with a fused per-query top-2; the
+//                       scan body (staging, tile loop, MFMA chain) is ia_k3_scan.h's
 //   ia_kernels.hip      K4 k_merge_level, k_merge_gather: exact fp64 rerank of the MFMA candidates
 //                       (numpy pairwise-sum order, lowest-index ties), certification with exact
 //                       fallback rescan, best_coherence_match (algorithms.py:92-130),
@@ -15,8 +16,9 @@
 //   ia_merge_shard.hip  k_finish_level, k_merge_xchg: the merges of a sharded level
 //   ia_dense.hip        dense variants for the FLANN-compatible index (ia_index_*), statistics,
 //                       stamps, microbenchmark operands
-//   ia_k3r.hip          the index's fixed-radius search: K3's scan with a threshold epilogue (count
-//                       and fill passes), exact verification, per-query sort (ia_index_*_radius)
+//   ia_k3r.hip          the index's fixed-radius search: the same scan body (ia_k3_scan.h) with a
+//                       threshold epilogue (count and fill passes), exact verification, per-query
+//                       sort (ia_index_*_radius)
 //
 // Here: feature geometry and access, numpy's and OpenBLAS's summation orders, the wave
 // reductions, the exact row distances and the certification bounds; at the end the two host
@@ -304,6 +306,14 @@ __device__ double pw_sum_rt(T &&term, int n) {
   int n2 = n / 2;
   n2 -= n2 % 8;
   return pw_block_rt(term, 0, n2) + pw_block_rt(term, n2, n - n2);
+}
+// exact squared distance of a row and a query of the index (n doubles each), in numpy's order:
+// every exact distance of ia_index_* (the merges, the radius verification, the coherence batch)
+__device__ __forceinline__ double row_dist2_rt(const double *a, const double *q, int n) {
+  return pw_sum_rt([&](int f) {
+    const double x = a[f] - q[f];
+    return x * x;
+  }, n);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -214,3 +215,31 @@ struct __attribute__((visibility("hidden"))) ia_index {
   int64_t workspace = 0;                  // ia_index_set_workspace: candidate entries per fill pass (0: default)
   int64_t radius_stats[4] = {0, 0, 0, 0};  // the last radius call (ia_index_radius_stats)
 };
+
+// the index's query driver (ia_index.cpp), shared by ia_index_query, ia_index_query_knn and the
+// radius search (ia_index_radius.cpp)
+namespace ia_host __attribute__((visibility("hidden"))) {
+
+static constexpr int64_t IA_INDEX_BATCH = 4096;  // queries scanned against the DB at a time
+
+// the prescaled fp32 copy of a query must stay far inside fp32: refuses (as entry point who) queries
+// farther than 2^100 times the rows' spread from their mean (the rows themselves are <= 1 there),
+// and NaN / inf
+int index_check_queries(const ia_index *x, const std::string &who, const double *q, int64_t nq);
+// allocates x->q, x->qn2 and x->qf for the batches of nq queries; every entry point's first
+// allocation, before it takes a device pointer of the index
+int index_reserve_batch(ia_index *x, int64_t nq);
+// the merge arguments of an index: its records (x->rec, x->recT, x->qn2 as allocated now) over the whole DB
+MergeArgs index_merge_args(const ia_index *x);
+// per batch of IA_INDEX_BATCH queries: uploads the queries b0 .. b0 + nb to x->q, builds x->qn2 and
+// x->qf (Mpad = nb padded to qtt query tiles), then body(b0, nb, Mpad, qtt), which enqueues its scans
+// and merge, copies its results and waits for the stream; stops at the first status that is not IA_OK
+int index_for_batches(ia_index *x, const double *q, int64_t nq, const std::function<int(int64_t, int, int, int)> &body);
+// the query tiles [qta, qtb) in launches of at most ia_k3_qtmax(KH): launch(first tile, tiles)
+template <class F>
+void index_scan_tiles(const ia_index *x, int qta, int qtb, F &&launch) {
+  const int qtmax = ia_k3_qtmax(x->KH);
+  for (int qt0 = qta; qt0 < qtb; qt0 += qtmax) launch(qt0, std::min(qtmax, qtb - qt0));
+}
+
+}  // namespace ia_host

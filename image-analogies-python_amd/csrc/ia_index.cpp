@@ -7,6 +7,77 @@
 
 using namespace ia_host;
 
+// ------------------------------------------------------------------------------------------
+// the index's query driver (declared in ia_host.h): what ia_index_query, ia_index_query_knn and
+// the radius search (ia_index_radius.cpp) do alike
+// ------------------------------------------------------------------------------------------
+namespace ia_host {
+
+int index_check_queries(const ia_index *x, const std::string &who, const double *q, int64_t nq) {
+  for (int64_t i = 0; i < nq; i++)
+    for (int f = 0; f < x->d; f++)
+      if (!(std::fabs((q[i * x->d + f] - x->mu_h[f]) * x->sc) <= 0x1p100))
+        return fail(IA_EINVAL, who + ": query " + std::to_string(i) +
+                                   " is not finite or farther than 2^100 x the rows' spread from their mean");
+  return IA_OK;
+}
+
+MergeArgs index_merge_args(const ia_index *x) {
+  MergeArgs ma;
+  ma.db64 = nullptr;
+  ma.rec = x->rec.as<float4>();
+  ma.recT = x->recT.as<float>();
+  ma.q64 = nullptr;
+  ma.qn2 = x->qn2.as<double>();
+  ma.Rbits = x->Rbits.as<unsigned>();
+  ma.nwg = x->nwg;
+  ma.tpw = x->tpw;
+  ma.pos0 = 0;
+  ma.pos_end = x->n_tiles * IA_TILE;
+  ma.NT = x->n_tiles;
+  ma.NA = (int)x->n;
+  ma.pos2row = nullptr;
+  ma.rr = 0;
+  ma.qinfo = nullptr;
+  ma.boxes = nullptr;
+  ma.ufac = 0.;
+  ma.img_rows = 0;
+  ma.eps_c = ia_eps_c(2 * x->KH);
+  ma.eps_a = 0.;
+  return ma;
+}
+
+int index_reserve_batch(ia_index *x, int64_t nq) {
+  const int64_t bmax = std::min(nq, IA_INDEX_BATCH), bpad = tile_pad(bmax);
+  int rc;
+  if ((rc = x->q.ensure((size_t)bmax * x->d * 8)) || (rc = x->qn2.ensure((size_t)bpad * 8)) ||
+      (rc = x->qf.ensure((size_t)bpad * 2 * x->KH * 4)))
+    return rc;
+  return IA_OK;
+}
+
+int index_for_batches(ia_index *x, const double *q, int64_t nq, const std::function<int(int64_t, int, int, int)> &body) {
+  ia_ctx *c = x->ctx;
+  for (int64_t b0 = 0; b0 < nq; b0 += IA_INDEX_BATCH) {
+    const int nb = (int)std::min(IA_INDEX_BATCH, nq - b0), Mpad = (int)tile_pad(nb);
+    HIP_TRY(hipMemcpyAsync(x->q.p, q + b0 * x->d, (size_t)nb * x->d * 8, hipMemcpyHostToDevice, c->st));
+    ia_launch_dense_query(x->KH, x->q.as<double>(), nb, x->d, Mpad, x->mu.as<double>(), x->sc, x->qn2.as<double>(),
+                          x->qf.as<float>(), c->st);
+    if (int rc = body(b0, nb, Mpad, Mpad / IA_TILE)) return rc;
+  }
+  return IA_OK;
+}
+
+}  // namespace ia_host
+
+// the top-2 scan of a batch's nb queries (qtt query tiles) into x->rec / x->recT
+static void index_scan_top2(ia_index *x, int nb, int qtt) {
+  index_scan_tiles(x, 0, qtt, [&](int qt0, int qt) {
+    ia_launch_k3(x->KH, qt, x->db.as<float4>(), x->qf.as<float4>(), x->n_tiles, x->tpw, qt0, nb, x->nwg, 0, x->n_tiles,
+                 x->rec.as<float4>(), x->recT.as<float>(), x->ctx->st);
+  });
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------
@@ -178,66 +249,26 @@ int ia_index_query(ia_index *x, const double *q, int64_t nq, int64_t *idx_out, d
   if (!x || !q || !idx_out || nq < 0) return fail(IA_EINVAL, "ia_index_query: bad arguments");
   if (nq == 0) return IA_OK;
   ia_ctx *c = x->ctx;
-  // the prescaled fp32 copy of a query must stay far inside fp32: refuse queries farther than 2^100
-  // times the rows' spread from their mean (the rows themselves are <= 1 there), and NaN / inf
-  for (int64_t i = 0; i < nq; i++)
-    for (int f = 0; f < x->d; f++)
-      if (!(std::fabs((q[i * x->d + f] - x->mu_h[f]) * x->sc) <= 0x1p100))
-        return fail(IA_EINVAL, "ia_index_query: query " + std::to_string(i) +
-                                   " is not finite or farther than 2^100 x the rows' spread from their mean");
-  HIP_TRY(hipSetDevice(c->dev));
-  const int64_t BATCH = 4096;
-  const int64_t bmax = std::min(nq, BATCH), bpad = (bmax + IA_TILE - 1) / IA_TILE * IA_TILE;
-  const int DP = 2 * x->KH;
   int rc;
-  if ((rc = x->q.ensure((size_t)bmax * x->d * 8)) || (rc = x->qn2.ensure((size_t)bpad * 8)) ||
-      (rc = x->qf.ensure((size_t)bpad * DP * 4)) || (rc = x->rec.ensure((size_t)bmax * x->nwg * 16)) ||
-      (rc = x->recT.ensure((size_t)bmax * x->nwg * 4)) || (rc = x->idx.ensure((size_t)bmax * 8)) ||
-      (rc = x->dist.ensure((size_t)bmax * 8)))
+  if ((rc = index_check_queries(x, "ia_index_query", q, nq))) return rc;
+  HIP_TRY(hipSetDevice(c->dev));
+  const int64_t bmax = std::min(nq, IA_INDEX_BATCH);
+  if ((rc = index_reserve_batch(x, nq)) || (rc = x->rec.ensure((size_t)bmax * x->nwg * 16)) ||
+      (rc = x->recT.ensure((size_t)bmax * x->nwg * 4)) ||
+      (rc = x->idx.ensure((size_t)bmax * 8)) || (rc = x->dist.ensure((size_t)bmax * 8)))
     return rc;
   HIP_TRY(hipMemsetAsync(x->counters.p, 0, 32, c->st));
-  MergeArgs ma;
-  ma.db64 = nullptr;
-  ma.rec = x->rec.as<float4>();
-  ma.recT = x->recT.as<float>();
-  ma.q64 = nullptr;
-  ma.qn2 = x->qn2.as<double>();
-  ma.Rbits = x->Rbits.as<unsigned>();
-  ma.nwg = x->nwg;
-  ma.tpw = x->tpw;
-  ma.pos0 = 0;
-  ma.pos_end = x->n_tiles * IA_TILE;
-  ma.NT = x->n_tiles;
-  ma.NA = (int)x->n;
-  ma.pos2row = nullptr;
-  ma.rr = 0;
-  ma.qinfo = nullptr;
-  ma.boxes = nullptr;
-  ma.ufac = 0.;
-  ma.img_rows = 0;
-  ma.eps_c = ia_eps_c(DP);
-  ma.eps_a = 0.;
-  const int qtmax = ia_k3_qtmax(x->KH);
-  for (int64_t b0 = 0; b0 < nq; b0 += BATCH) {
-    const int64_t nb = std::min(BATCH, nq - b0);
-    const int Mpad = (int)((nb + IA_TILE - 1) / IA_TILE * IA_TILE);
-    HIP_TRY(hipMemcpyAsync(x->q.p, q + b0 * x->d, (size_t)nb * x->d * 8, hipMemcpyHostToDevice, c->st));
-    ia_launch_dense_query(x->KH, x->q.as<double>(), nb, x->d, Mpad, x->mu.as<double>(), x->sc, x->qn2.as<double>(),
-                          x->qf.as<float>(), c->st);
-    const int qtt = Mpad / IA_TILE;
-    for (int qt0 = 0; qt0 < qtt; qt0 += qtmax) {
-      const int qt = std::min(qtmax, qtt - qt0);
-      ia_launch_k3(x->KH, qt, x->db.as<float4>(), x->qf.as<float4>(), x->n_tiles, x->tpw, qt0, (int)nb, x->nwg, 0, x->n_tiles,
-                   x->rec.as<float4>(), x->recT.as<float>(), c->st);
-    }
+  const MergeArgs ma = index_merge_args(x);
+  return index_for_batches(x, q, nq, [&](int64_t b0, int nb, int, int qtt) -> int {
+    index_scan_top2(x, nb, qtt);
     ia_launch_merge_dense(ma, x->pts.as<double>(), x->d, x->q.as<double>(), nb, x->sc * x->sc, x->idx.as<int64_t>(),
                           x->dist.as<double>(), c->st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(idx_out + b0, x->idx.p, (size_t)nb * 8, hipMemcpyDeviceToHost, c->st));
     if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out + b0, x->dist.p, (size_t)nb * 8, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
-  }
-  return IA_OK;
+    return IA_OK;
+  });
 }
 
 // nn_index(q, k): ia_index_query's batches and scans, merged by k_merge_dense_knn (ia_topk.h)
@@ -246,69 +277,31 @@ int ia_index_query_knn(ia_index *x, const double *q, int64_t nq, int k, int64_t 
   if (k < 1 || k > IA_KNN_MAX || k > x->n)
     return fail(IA_EINVAL, "ia_index_query_knn: k must be 1.." + std::to_string(std::min<int64_t>(IA_KNN_MAX, x->n)) +
                                " (IA_KNN_MAX and the index's rows)");
-  for (int64_t i = 0; i < nq; i++)  // ia_index_query's rule
-    for (int f = 0; f < x->d; f++)
-      if (!(std::fabs((q[i * x->d + f] - x->mu_h[f]) * x->sc) <= 0x1p100))
-        return fail(IA_EINVAL, "ia_index_query_knn: query " + std::to_string(i) +
-                                   " is not finite or farther than 2^100 x the rows' spread from their mean");
+  int rc;
+  if ((rc = index_check_queries(x, "ia_index_query_knn", q, nq))) return rc;
   x->knn_stats[0] = x->knn_stats[1] = 0;
   if (nq == 0) return IA_OK;
   ia_ctx *c = x->ctx;
   HIP_TRY(hipSetDevice(c->dev));
-  const int64_t BATCH = 4096;
-  const int64_t bmax = std::min(nq, BATCH), bpad = (bmax + IA_TILE - 1) / IA_TILE * IA_TILE;
-  const int DP = 2 * x->KH;
-  int rc;
-  if ((rc = x->q.ensure((size_t)bmax * x->d * 8)) || (rc = x->qn2.ensure((size_t)bpad * 8)) ||
-      (rc = x->qf.ensure((size_t)bpad * DP * 4)) || (rc = x->rec.ensure((size_t)bmax * x->nwg * 16)) ||
-      (rc = x->recT.ensure((size_t)bmax * x->nwg * 4)) || (rc = x->idx.ensure((size_t)bmax * k * 8)) ||
-      (rc = x->dist.ensure((size_t)bmax * k * 8)))
+  const int64_t bmax = std::min(nq, IA_INDEX_BATCH);
+  if ((rc = index_reserve_batch(x, nq)) || (rc = x->rec.ensure((size_t)bmax * x->nwg * 16)) ||
+      (rc = x->recT.ensure((size_t)bmax * x->nwg * 4)) ||
+      (rc = x->idx.ensure((size_t)bmax * k * 8)) || (rc = x->dist.ensure((size_t)bmax * k * 8)))
     return rc;
   HIP_TRY(hipMemsetAsync(x->counters.p, 0, 32, c->st));
-  MergeArgs ma;
-  ma.db64 = nullptr;
-  ma.rec = x->rec.as<float4>();
-  ma.recT = x->recT.as<float>();
-  ma.q64 = nullptr;
-  ma.qn2 = x->qn2.as<double>();
-  ma.Rbits = x->Rbits.as<unsigned>();
-  ma.nwg = x->nwg;
-  ma.tpw = x->tpw;
-  ma.pos0 = 0;
-  ma.pos_end = x->n_tiles * IA_TILE;
-  ma.NT = x->n_tiles;
-  ma.NA = (int)x->n;
-  ma.pos2row = nullptr;
-  ma.rr = 0;
-  ma.qinfo = nullptr;
-  ma.boxes = nullptr;
-  ma.ufac = 0.;
-  ma.img_rows = 0;
-  ma.eps_c = ia_eps_c(DP);
-  ma.eps_a = 0.;
-  const int qtmax = ia_k3_qtmax(x->KH);
-  for (int64_t b0 = 0; b0 < nq; b0 += BATCH) {
-    const int64_t nb = std::min(BATCH, nq - b0);
-    const int Mpad = (int)((nb + IA_TILE - 1) / IA_TILE * IA_TILE);
-    HIP_TRY(hipMemcpyAsync(x->q.p, q + b0 * x->d, (size_t)nb * x->d * 8, hipMemcpyHostToDevice, c->st));
-    ia_launch_dense_query(x->KH, x->q.as<double>(), nb, x->d, Mpad, x->mu.as<double>(), x->sc, x->qn2.as<double>(),
-                          x->qf.as<float>(), c->st);
-    const int qtt = Mpad / IA_TILE;
-    for (int qt0 = 0; qt0 < qtt; qt0 += qtmax) {
-      const int qt = std::min(qtmax, qtt - qt0);
-      ia_launch_k3(x->KH, qt, x->db.as<float4>(), x->qf.as<float4>(), x->n_tiles, x->tpw, qt0, (int)nb, x->nwg, 0, x->n_tiles,
-                   x->rec.as<float4>(), x->recT.as<float>(), c->st);
-    }
+  const MergeArgs ma = index_merge_args(x);
+  return index_for_batches(x, q, nq, [&](int64_t b0, int nb, int, int qtt) -> int {
+    index_scan_top2(x, nb, qtt);
     ia_launch_merge_dense_knn(ma, x->pts.as<double>(), x->d, x->q.as<double>(), nb, k, x->sc * x->sc, x->idx.as<int64_t>(),
                               x->dist.as<double>(), x->counters.as<unsigned long long>(), c->st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(idx_out + b0 * k, x->idx.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, c->st));
     if (dist_out) HIP_TRY(hipMemcpyAsync(dist_out + b0 * k, x->dist.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, c->st));
-    if (b0 + BATCH >= nq)  // the sums over every batch, with the last results
+    if (b0 + nb == nq)  // the sums over every batch, with the last results
       HIP_TRY(hipMemcpyAsync(x->knn_stats, x->counters.p, 16, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
-  }
-  return IA_OK;
+    return IA_OK;
+  });
 }
 
 int ia_index_knn_stats(const ia_index *x, int64_t out[2]) {

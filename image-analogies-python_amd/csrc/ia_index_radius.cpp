@@ -2,10 +2,10 @@
 // ia_index_count_radius, ia_index_query_radius, ia_index_set_workspace, ia_index_radius_stats.
 // Kernels in ia_k3r.hip; the argument in DESIGN.md §5 "Radius queries".
 //
-// Per batch of 4,096 queries: thresholds, the counting scan, per-query offsets; the host reads the
-// per-query candidate totals and cuts the batch into sub-batches of consecutive queries whose
-// candidates fit the workspace; per sub-batch the filling scan, the exact fp64 verification, the
-// per-query sort and count, and one copy of the staged results.
+// Per batch of queries (ia_index.cpp's driver, as for ia_index_query): thresholds, the counting
+// scan, per-query offsets; the host reads the per-query candidate totals and cuts the batch into
+// sub-batches of consecutive queries whose candidates fit the workspace; per sub-batch the filling
+// scan, the exact fp64 verification, the per-query sort and count, and one copy of the staged results.
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -16,7 +16,6 @@ using namespace ia_host;
 
 namespace {
 
-constexpr int64_t R_BATCH = 4096;
 constexpr int64_t R_WORKSPACE_DEFAULT = (int64_t)1 << 23;  // candidate entries (12 B each on the device)
 constexpr int64_t R_WORKSPACE_MAX = 0xffffff00LL;          // offsets inside a sub-batch are 32-bit
 
@@ -38,28 +37,22 @@ int radius_run(ia_index *x, const std::string &who, const double *q, int64_t nq,
   }
   for (int64_t i = 0; i < nq; i++)
     if (!(radius[i] >= 0.)) return fail(IA_EINVAL, who + ": radius " + std::to_string(i) + " is negative or NaN");
-  for (int64_t i = 0; i < nq; i++)  // ia_index_query's rule
-    for (int f = 0; f < x->d; f++)
-      if (!(std::fabs((q[i * x->d + f] - x->mu_h[f]) * x->sc) <= 0x1p100))
-        return fail(IA_EINVAL, who + ": query " + std::to_string(i) +
-                                   " is not finite or farther than 2^100 x the rows' spread from their mean");
+  int rc;
+  if ((rc = index_check_queries(x, who, q, nq))) return rc;
   int64_t *stats = x->radius_stats;
   stats[0] = stats[1] = stats[2] = stats[3] = 0;
   if (nq == 0) return IA_OK;
   ia_ctx *c = x->ctx;
   HIP_TRY(hipSetDevice(c->dev));
-  const int64_t bmax = std::min(nq, R_BATCH), bpad = tile_pad(bmax);
-  const int DP = 2 * x->KH, NT = x->n_tiles, nwg = x->nwg;
-  int rc;
-  if ((rc = x->q.ensure((size_t)bmax * x->d * 8)) || (rc = x->qn2.ensure((size_t)bpad * 8)) ||
-      (rc = x->qf.ensure((size_t)bpad * DP * 4)) || (rc = x->r_rad.ensure((size_t)bmax * 8)) ||
-      (rc = x->r_thr.ensure((size_t)bpad * 8)) || (rc = x->r_cnt.ensure((size_t)bpad * nwg * 8)) ||
-      (rc = x->r_seg.ensure((size_t)bpad * nwg * 8)) || (rc = x->r_ts.ensure((size_t)bmax * 8)) ||
-      (rc = x->r_qoff.ensure((size_t)bmax * 4)) || (rc = x->r_soff.ensure((size_t)(bmax + 1) * 4)) ||
-      (rc = x->r_cntq.ensure((size_t)bmax * 8)))
+  const int64_t bmax = std::min(nq, IA_INDEX_BATCH), bpad = tile_pad(bmax);
+  const int NT = x->n_tiles, nwg = x->nwg;
+  if ((rc = index_reserve_batch(x, nq)) || (rc = x->r_rad.ensure((size_t)bmax * 8)) || (rc = x->r_thr.ensure((size_t)bpad * 8)) ||
+      (rc = x->r_cnt.ensure((size_t)bpad * nwg * 8)) || (rc = x->r_seg.ensure((size_t)bpad * nwg * 8)) ||
+      (rc = x->r_ts.ensure((size_t)bmax * 8)) || (rc = x->r_qoff.ensure((size_t)bmax * 4)) ||
+      (rc = x->r_soff.ensure((size_t)(bmax + 1) * 4)) || (rc = x->r_cntq.ensure((size_t)bmax * 8)))
     return rc;
   const int64_t W = effective_workspace(x);
-  const int qtmax = ia_k3_qtmax(x->KH), sort_lds = ia_k3r_sort_lds();
+  const int sort_lds = ia_k3r_sort_lds();
   const float4 *db = x->db.as<float4>(), *qf = x->qf.as<float4>();
   const float2 *thr = x->r_thr.as<float2>();
   const uint2 *ts_d = x->r_ts.as<uint2>();
@@ -67,16 +60,13 @@ int radius_run(ia_index *x, const std::string &who, const double *q, int64_t nq,
   std::vector<unsigned> qoff(bmax), soff(bmax + 1);
   std::vector<int64_t> cntq(bmax), st_idx;
   std::vector<double> st_dist;
-  for (int64_t b0 = 0; b0 < nq; b0 += R_BATCH) {
-    const int nb = (int)std::min(R_BATCH, nq - b0), Mpad = (int)tile_pad(nb), qtt = Mpad / IA_TILE;
-    HIP_TRY(hipMemcpyAsync(x->q.p, q + b0 * x->d, (size_t)nb * x->d * 8, hipMemcpyHostToDevice, c->st));
+  return index_for_batches(x, q, nq, [&](int64_t b0, int nb, int Mpad, int qtt) -> int {
     HIP_TRY(hipMemcpyAsync(x->r_rad.p, radius + b0, (size_t)nb * 8, hipMemcpyHostToDevice, c->st));
-    ia_launch_dense_query(x->KH, x->q.as<double>(), nb, x->d, Mpad, x->mu.as<double>(), x->sc, x->qn2.as<double>(),
-                          x->qf.as<float>(), c->st);
     ia_launch_k3r_thresholds(x->r_rad.as<double>(), x->qn2.as<double>(), x->Rbits.as<unsigned>(), nb, Mpad, x->sc * x->sc,
-                             ia_eps_c(DP), x->r_thr.as<float2>(), c->st);
-    for (int qt0 = 0; qt0 < qtt; qt0 += qtmax)
-      ia_launch_k3r_count(x->KH, std::min(qtmax, qtt - qt0), db, qf, thr, NT, x->tpw, qt0, nb, nwg, x->r_cnt.as<uint2>(), c->st);
+                             ia_eps_c(2 * x->KH), x->r_thr.as<float2>(), c->st);
+    index_scan_tiles(x, 0, qtt, [&](int qt0, int qt) {
+      ia_launch_k3r_count(x->KH, qt, db, qf, thr, NT, x->tpw, qt0, nb, nwg, x->r_cnt.as<uint2>(), c->st);
+    });
     ia_launch_k3r_offsets(x->r_cnt.as<uint2>(), nb, nwg, count_only, x->r_seg.as<uint2>(), x->r_ts.as<uint2>(), c->st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ts.data(), x->r_ts.p, (size_t)nb * 8, hipMemcpyDeviceToHost, c->st));
@@ -109,10 +99,11 @@ int radius_run(ia_index *x, const std::string &who, const double *q, int64_t nq,
       HIP_TRY(hipMemcpyAsync(x->r_qoff.as<unsigned>() + j0, &qoff[j0], (size_t)(j1 - j0) * 4, hipMemcpyHostToDevice, c->st));
       HIP_TRY(hipMemcpyAsync(x->r_soff.as<unsigned>() + j0, &soff[j0], (size_t)(j1 - j0 + 1) * 4, hipMemcpyHostToDevice, c->st));
       if (sum > 0) {
-        const int qta = j0 / IA_TILE, qtb = (j1 - 1) / IA_TILE + 1;  // the query tiles that hold [j0, j1)
-        for (int qt0 = qta; qt0 < qtb; qt0 += qtmax)
-          ia_launch_k3r_fill(x->KH, std::min(qtmax, qtb - qt0), count_only, db, qf, thr, NT, x->tpw, qt0, j0, j1, nwg,
-                             x->r_seg.as<uint2>(), qoff_d, x->r_wr.as<int>(), c->st);
+        // the query tiles that hold [j0, j1)
+        index_scan_tiles(x, j0 / IA_TILE, (j1 - 1) / IA_TILE + 1, [&](int qt0, int qt) {
+          ia_launch_k3r_fill(x->KH, qt, count_only, db, qf, thr, NT, x->tpw, qt0, j0, j1, nwg, x->r_seg.as<uint2>(), qoff_d,
+                             x->r_wr.as<int>(), c->st);
+        });
         ia_launch_k3r_verify(x->pts.as<double>(), x->n, x->d, NT, x->q.as<double>(), x->r_rad.as<double>(), ts_d, qoff_d, j0, j1,
                              max_len, x->r_wr.as<int>(), x->r_wd.as<double>(), c->st);
         stats[2]++;
@@ -149,8 +140,8 @@ int radius_run(ia_index *x, const std::string &who, const double *q, int64_t nq,
         }
       }
     }
-  }
-  return IA_OK;
+    return IA_OK;
+  });
 }
 
 }  // namespace

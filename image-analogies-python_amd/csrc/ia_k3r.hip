@@ -3,9 +3,9 @@
 //
 //   k3r_thresholds  per query two fp32 thresholds on the scan's MFMA value: every row inside the
 //                   radius has value <= hi, every row with value <= lo is inside
-//   k3r_count       K3's scan (ia_k3.hip k3_dist: same geometry, same MFMA chain, restated) with the
-//                   top-2 epilogue replaced by a threshold test: per (query, workgroup) the number of
-//                   values <= lo and <= hi
+//   k3r_count       K3's scan (ia_k3_scan.h k3_scan, the body k3_dist runs: one text, so the same
+//                   geometry and MFMA chain) with a threshold test for epilogue: per (query,
+//                   workgroup) the number of values <= lo and <= hi
 //   k3r_offsets     per query the prefix sums of its workgroups' counts: private output segments
 //   k3r_fill        the same scan again; a hit takes the next slot of its workgroup's segment
 //   k3r_verify      the exact fp64 distance (numpy's pairwise order) of every appended (query, row)
@@ -15,6 +15,7 @@
 // no global atomic anywhere (the only atomics are LDS slot counters), so the counts are
 // deterministic and the candidates of one query are contiguous for the sort.
 #include "ia_dev.h"
+#include "ia_k3_scan.h"
 #include "ia_launch.h"
 
 #define IA_R_LO_MAX 1.0e29  // lo never reaches IA_PAD_NORM: a padding row is never "certainly inside"
@@ -56,96 +57,21 @@ __global__ void __launch_bounds__(IA_WG) k3r_thresholds(const double *__restrict
 }
 
 // ------------------------------------------------------------------------------------------
-// the scan: k3_dist's loop (ia_k3.hip) restated.  grid.x = nwg workgroups of 4 waves; workgroup w
-// owns DB tiles [w*tpw, (w+1)*tpw), wave v takes tiles w*tpw + v, +4, ...; QT query tiles staged in
-// LDS once; each DB tile is loaded once into registers and contracted against every query tile;
-// C layout: lane holds query (lane & 31), positions (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the
-// tile, r = 0..15.  Epilogue per accumulator: the minimum of its 16 values against the lane's hi;
+// the scan: ia_k3_scan.h's k3_scan (k3_dist's own body: geometry and C layout there) with a
+// threshold epilogue.  Per accumulator: the minimum of its 16 values against the lane's hi;
 // hit(acc, q, m, pbase) runs, wave-uniformly, only where some lane has a value <= hi (m: this
 // lane's minimum, pbase: the position of acc[0]).
 // ------------------------------------------------------------------------------------------
 template <int KH, int QT, class Hit>
 __device__ __forceinline__ void k3r_scan(const float4 *__restrict__ db, const float4 *lds, int n_tiles, int tpw,
                                          const float (&hi)[QT], Hit &&hit) {
-  constexpr int KP = KH / 4;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
-  const int wg = blockIdx.x;
-  const int t_begin = wg * tpw, t_end = min(n_tiles, t_begin + tpw);
-  int t = t_begin + wave;
-  float a[KH], an[KH];
-  {
-    const int tl = min(t, n_tiles - 1);
-    const float4 *src = db + (int64_t)tl * KP * IA_WAVE + lane;
+  k3_scan<KH, QT>(db, lds, n_tiles, tpw, [&](const f32x16 &acc, int q, int pbase) {
+    float m = fminf(fminf(acc[0], acc[1]), acc[2]);  // v_min3_f32 chain
 #pragma unroll
-    for (int p = 0; p < KP; p++) {
-      float4 v = src[p * IA_WAVE];
-      a[4 * p] = v.x; a[4 * p + 1] = v.y; a[4 * p + 2] = v.z; a[4 * p + 3] = v.w;
-    }
-  }
-  for (; t < t_end; t += 4) {
-    {  // prefetch the next tile of this wave (clamped: always issue, never branch per load)
-      const int tl = min(t + 4, n_tiles - 1);
-      const float4 *src = db + (int64_t)tl * KP * IA_WAVE + lane;
-#pragma unroll
-      for (int p = 0; p < KP; p++) {
-        float4 v = src[p * IA_WAVE];
-        an[4 * p] = v.x; an[4 * p + 1] = v.y; an[4 * p + 2] = v.z; an[4 * p + 3] = v.w;
-      }
-    }
-    const int pbase = t * IA_TILE + 4 * half;
-    asm volatile("" ::: "memory");  // LDS query fragments are re-read per tile, not hoisted
-    f32x16 e0, e1;
-    auto epilogue = [&](const f32x16 &acc, int q) {
-      float m = fminf(fminf(acc[0], acc[1]), acc[2]);  // v_min3_f32 chain
-#pragma unroll
-      for (int r = 3; r < 15; r += 2) m = fminf(fminf(m, acc[r]), acc[r + 1]);
-      m = fminf(m, acc[15]);
-      if (__any(m <= hi[q])) hit(acc, q, m, pbase);
-    };
-#pragma unroll
-    for (int qp = 0; qp < QT; qp += 2) {
-      constexpr f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      const bool two = qp + 1 < QT;
-      f32x16 c0 = zero, c1 = zero;
-      const float4 *qb0 = lds + qp * KP * IA_WAVE + lane;
-      const float4 *qb1 = qb0 + KP * IA_WAVE;
-#pragma unroll
-      for (int p = 0; p < KP; p++) {
-        const float4 x0 = qb0[p * IA_WAVE];
-        const float4 x1 = two ? qb1[p * IA_WAVE] : x0;
-        c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * p], x0.x, c0, 0, 0, 0);
-        if (two) c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * p], x1.x, c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * p + 1], x0.y, c0, 0, 0, 0);
-        if (two) c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * p + 1], x1.y, c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * p + 2], x0.z, c0, 0, 0, 0);
-        if (two) c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * p + 2], x1.z, c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * p + 3], x0.w, c0, 0, 0, 0);
-        if (two) c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * p + 3], x1.w, c1, 0, 0, 0);
-      }
-      if (qp >= 2) {
-        epilogue(e0, qp - 2);
-        epilogue(e1, qp - 1);
-      }
-      e0 = c0;
-      e1 = c1;
-    }
-    {
-      constexpr int ql = ((QT - 1) / 2) * 2;  // first tile of the last pair
-      epilogue(e0, ql);
-      if (ql + 1 < QT) epilogue(e1, ql + 1);
-    }
-#pragma unroll
-    for (int k = 0; k < KH; k++) a[k] = an[k];
-  }
-}
-
-// stage the launch's QT query tiles in LDS (every thread; ends with a barrier)
-template <int KH, int QT>
-__device__ __forceinline__ void k3r_stage(const float4 *__restrict__ qf, int qt0, float4 *lds) {
-  constexpr int KP = KH / 4;
-  const float4 *qsrc = qf + (int64_t)qt0 * KP * IA_WAVE;
-  for (int i = threadIdx.x; i < QT * KP * IA_WAVE; i += IA_WG) lds[i] = qsrc[i];
-  __syncthreads();
+    for (int r = 3; r < 15; r += 2) m = fminf(fminf(m, acc[r]), acc[r + 1]);
+    m = fminf(m, acc[15]);
+    if (__any(m <= hi[q])) hit(acc, q, m, pbase);
+  });
 }
 
 // pass 1: cnt[q nwg + wg] = (values <= lo, values <= hi) of query q in workgroup wg's tiles
@@ -155,7 +81,7 @@ k3r_count(const float4 *__restrict__ db, const float4 *__restrict__ qf, const fl
           int qt0, int M, int nwg, uint2 *__restrict__ cnt) {
   extern __shared__ float4 lds[];  // QT * KP * 64 float4 (queries), reused for the reduction
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
-  k3r_stage<KH, QT>(qf, qt0, lds);
+  k3_stage<KH, QT>(qf, qt0, lds);
   float hi[QT];
   unsigned nlo[QT], nhi[QT];
 #pragma unroll
@@ -224,9 +150,9 @@ __global__ void __launch_bounds__(IA_WG) k3r_offsets(const uint2 *__restrict__ c
 
 // pass 2 over the queries [j0, j1) of the batch (every other query of a loaded tile: hi =
 // -FLT_MAX): a hit takes slot seg[(q, wg)].start + (LDS counter of q)++ of the query's candidates,
-// which start at qoff[q] in cand, and stores its tile position.  The same MFMA chain on the same
-// operands as pass 1 gives the same values, so the counter ends at the segment's length; a slot
-// beyond it is dropped all the same (never written).
+// which start at qoff[q] in cand, and stores its tile position.  The same MFMA chain (k3_scan, one
+// text for both passes) on the same operands as pass 1 gives the same values, so the counter ends
+// at the segment's length; a slot beyond it is dropped all the same (never written).
 template <int KH, int QT, bool COUNT_ONLY>
 __global__ void __launch_bounds__(IA_WG, 2)
 k3r_fill(const float4 *__restrict__ db, const float4 *__restrict__ qf, const float2 *__restrict__ thr, int n_tiles, int tpw,
@@ -237,7 +163,7 @@ k3r_fill(const float4 *__restrict__ db, const float4 *__restrict__ qf, const flo
   unsigned *slot = reinterpret_cast<unsigned *>(lds + QT * KP * IA_WAVE);
   const int lane = threadIdx.x & 63;
   for (int i = threadIdx.x; i < QT * IA_TILE; i += IA_WG) slot[i] = 0u;
-  k3r_stage<KH, QT>(qf, qt0, lds);
+  k3_stage<KH, QT>(qf, qt0, lds);
   float hi[QT];
 #pragma unroll
   for (int q = 0; q < QT; q++) {
@@ -279,11 +205,7 @@ __global__ void __launch_bounds__(IA_WG) k3r_verify(const double *__restrict__ p
     if ((unsigned)pos < (unsigned)NT * IA_TILE) {
       const int64_t row = ia_pos_row(pos, NT);
       if (row < n) {
-        const double *a = pts + row * d;
-        const double x2 = pw_sum_rt([&](int f) {
-          const double x = a[f] - qm[f];
-          return x * x;
-        }, d);
+        const double x2 = row_dist2_rt(pts + row * d, qm, d);
         if (x2 < rad) {
           dd = x2;
           rr = (int)row;

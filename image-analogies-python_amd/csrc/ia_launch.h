@@ -1,6 +1,8 @@
 // ia_launch.h — host launchers of the kernels in ia_level_db.hip, ia_gather.hip, ia_k3.hip,
 // ia_kernels.hip (the per-step merges), ia_merge_shard.hip, ia_dense.hip, ia_k3r.hip, ia_prune.hip,
 // ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
+// ia_k3.hip and ia_k3r.hip scan with one body (ia_k3_scan.h): ia_launch_k3, ia_launch_k3r_count and
+// ia_launch_k3r_fill take the same geometry (n_tiles, tpw, nwg; qt <= ia_k3_qtmax(KH) tiles from qt0).
 #pragma once
 #include <hip/hip_runtime.h>
 
