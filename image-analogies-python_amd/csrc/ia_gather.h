@@ -161,7 +161,7 @@ __device__ __forceinline__ void handoff_wait(const HandSlot *hs, const NextStep 
 // The pruning record (uniform values) of a query with |q'|^2 = ss, projections p and exact U'
 // candidate distance u (DBL_MAX: no candidate); ksc the key scale, ufac the level's U' factor.
 // o0 / o1: the projection interval; o2: U' and the Morton key, and K3p's hi x hi block filter
-// bound (k3p_variant 14/15, ia_k3h.hip k3p_filtered): value bound
+// bound (ia_k3h.hip k3p_bound): value bound
 // z >= U' - |q'|^2 with the f32 rounding of z and of the kernel's lim = z + R_t (...)
 // (2^-22 (|q'|^2 + U')) and the subnormal / norm-column terms (2^-24 (16 |q'| + 300));
 // w = 2^-8 |q'| (twice the relative error term's |q'| part)

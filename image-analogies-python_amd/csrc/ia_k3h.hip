@@ -77,7 +77,7 @@ __device__ __forceinline__ void slot_hi(h16x8 (&h)[4], const h16x8 *slot, int la
 #ifndef IA_PROBE
 #define IA_PROBE 0
 #endif
-#if IA_PROBE & 16  // diagnostic build only: per-wave phase cycle sums of the pruned scan (K3p, V >= 1)
+#if IA_PROBE & 16  // diagnostic build only: per-wave phase cycle sums of the pruned scan (K3p)
 __device__ unsigned long long k3p_prof[24];
 #define K3P_T(x) do { __builtin_amdgcn_sched_barrier(0); x = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
@@ -239,47 +239,59 @@ k3h_scan(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, int n_tiles
 }
 
 // ------------------------------------------------------------------------------------------
-// K3p: the certified pruned scan (1 channel).  The level's DB is Morton-sorted
-// in the projection space of its top IA_NPC principal axes (ia_prune.hip: position -> row table
-// pos2row, per-tile projection boxes); K2p wrote each query's projection interval, bound U' and
-// key (ia_prune.h).  Per workgroup:
-//   1. rank-sort the step's queries by key in LDS (deterministic: ties by query index) and
-//      gather this launch's QT query tiles in sorted order, so a query tile is compact in
-//      projection space too; per query tile a bounding box of its intervals and max U'
-//   2. DB tiles round-robin: WG w, wave v takes tiles w + nwg*(v + NW*k) (the merge rescans the
-//      same chunk, MergeArgs::rr); per tile a need mask over the query tiles: a coarse
-//      tile-box test (lanes = query tiles), then for the survivors the per-query test
-//      LB(q, tile) <= U'_q (lanes = queries, ballot).  Tiles nobody needs are never loaded; the
-//      next needed tile is prefetched while the current one is contracted
-//   3. only the needed (DB tile, query tile) pairs run the 12-MFMA chain (two chains at once
-//      when both tiles of a query-tile pair are needed) with the packed-index epilogue
-//   4. per-query records as K3h, written to the queries' original slots with DB rows taken
-//      from pos2row; the WG adds its computed pair count to *pairs (flop accounting)
+// K3p: the certified pruned scan (1 channel): k3h_prune3 below, whose header lists
+// its phases; here the block products, the filter's bound and the pair walkers of its tile walks.
+// The level's DB is Morton-sorted in the projection space of its top IA_NPC principal axes
+// (ia_prune.hip: position -> row table pos2row, per-tile projection boxes); K2p wrote each query's
+// projection interval, bound U' and key (ia_prune.h).  A workgroup's chunk is the tiles
+// wg + nwg k, which the merge rescans (MergeArgs::rr).
 // Skipped rows are strictly farther than the query's coherence candidate (ia_prune.h), so
 // they can neither be nor tie the exact NN; K4's certification over the computed rows stands.
 // ------------------------------------------------------------------------------------------
+// The query fragments of a workgroup in LDS: the hi / lo piece of (query tile q, step s), the lane
+// offset in the base pointers.  Interleaved: [QT][2 KS][64], piece 2 s = hi, 2 s + 1 = lo (whole
+// and hi-only streams).  Split: [QT][KS][64] hi, the same for lo (two passes; the lo array is
+// staged for the second pass only).
 template <int KS>
-__device__ __forceinline__ f32x16 k3p_chain(const h16x8 (&a)[2 * KS], const h16x8 *qb) {
-  f32x16 c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+struct K3pQmixed {
+  const h16x8 *b;
+  __device__ __forceinline__ h16x8 hi(int q, int s) const { return (b + q * 2 * KS * IA_WAVE)[(2 * s) * IA_WAVE]; }
+  __device__ __forceinline__ h16x8 lo(int q, int s) const { return (b + q * 2 * KS * IA_WAVE)[(2 * s + 1) * IA_WAVE]; }
+};
+template <int KS>
+struct K3pQsplit {
+  const h16x8 *h, *l;
+  __device__ __forceinline__ h16x8 hi(int q, int s) const { return (h + q * KS * IA_WAVE)[s * IA_WAVE]; }
+  __device__ __forceinline__ h16x8 lo(int q, int s) const { return (l + q * KS * IA_WAVE)[s * IA_WAVE]; }
+};
+
+// The products of one (DB tile a, query tile q) block over a view v.  The full product is, per
+// step, lo_a x hi_q, hi_a x lo_q, hi_a x hi_q into one accumulator: this order defines the
+// records' values.  The filtered forms run hi x hi first (k3p_hh) and add the
+// two correction products afterwards (k3p_corr; the order's error bound: DESIGN.md §4d).
+__device__ __forceinline__ f32x16 k3p_zero() {
+  return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+}
+template <int KS, class V>
+__device__ __forceinline__ f32x16 k3p_full(const h16x8 (&a)[2 * KS], const V &v, int q) {
+  f32x16 c = k3p_zero();
 #pragma unroll
   for (int s = 0; s < KS; s++) {
-    const h16x8 xh = qb[(2 * s) * IA_WAVE], xl = qb[(2 * s + 1) * IA_WAVE];
+    const h16x8 xh = v.hi(q, s), xl = v.lo(q, s);
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], xh, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], xl, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], xh, c, 0, 0, 0);
   }
   return c;
 }
-template <int KS>
-__device__ __forceinline__ void k3p_chain2(const h16x8 (&a)[2 * KS], const h16x8 *qb0, const h16x8 *qb1, f32x16 &c0,
-                                           f32x16 &c1) {
-  constexpr f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  c0 = zero;
-  c1 = zero;
+// two blocks of one DB tile as two independent chains (they share each DB operand)
+template <int KS, class V>
+__device__ __forceinline__ void k3p_full2(const h16x8 (&a)[2 * KS], const V &v, int q0, int q1, f32x16 &c0, f32x16 &c1) {
+  c0 = k3p_zero();
+  c1 = k3p_zero();
 #pragma unroll
   for (int s = 0; s < KS; s++) {
-    const h16x8 x0h = qb0[(2 * s) * IA_WAVE], x0l = qb0[(2 * s + 1) * IA_WAVE];
-    const h16x8 x1h = qb1[(2 * s) * IA_WAVE], x1l = qb1[(2 * s + 1) * IA_WAVE];
+    const h16x8 x0h = v.hi(q0, s), x0l = v.lo(q0, s), x1h = v.hi(q1, s), x1l = v.lo(q1, s);
     c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], x0h, c0, 0, 0, 0);
     c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], x1h, c1, 0, 0, 0);
     c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], x0l, c0, 0, 0, 0);
@@ -288,6 +300,32 @@ __device__ __forceinline__ void k3p_chain2(const h16x8 (&a)[2 * KS], const h16x8
     c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], x1h, c1, 0, 0, 0);
   }
 }
+// hi x hi alone.  a: a whole tile ([2 KS], its even pieces) or its hi pieces ([KS]: ld_hi, slot_hi).
+// GROUPED: the KS LDS reads first (one wait), then the KS products
+template <int KS, bool GROUPED, int NA, class V>
+__device__ __forceinline__ f32x16 k3p_hh(const h16x8 (&a)[NA], const V &v, int q) {
+  static_assert(NA == KS || NA == 2 * KS, "hi pieces or a whole tile");
+  f32x16 c = k3p_zero();
+  h16x8 x[KS];
+#pragma unroll
+  for (int s = 0; s < KS; s++) x[s] = v.hi(q, s);
+#pragma unroll
+  for (int s = 0; s < KS; s++) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[NA / KS * s], x[s], c, 0, 0, 0);
+  if constexpr (GROUPED) {
+    __builtin_amdgcn_sched_group_barrier(0x100, KS, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, KS, 0);
+  }
+  return c;
+}
+template <int KS, class V>
+__device__ __forceinline__ void k3p_corr(const h16x8 (&a)[2 * KS], const V &v, int q, f32x16 &c) {
+#pragma unroll
+  for (int s = 0; s < KS; s++) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], v.hi(q, s), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], v.lo(q, s), c, 0, 0, 0);
+  }
+}
+
 // packed epilogue of one accumulator into one query's (b1, b2, tile)
 __device__ __forceinline__ void k3p_epi1(const f32x16 &e, int t, float &b1, float &b2, int &i1) {
   const float o = b1;
@@ -299,41 +337,46 @@ __device__ __forceinline__ void k3p_epi1(const f32x16 &e, int t, float &b1, floa
   }
   i1 = b1 != o ? t : i1;
 }
-// query-tile pairs QP.. of one DB tile t; m2 = the pair's two need bits (wave-uniform).  A pair
-// with one needed tile runs one chain on it; its query state is selected with v_cndmask (never
-// a dynamically indexed register array, which would live in scratch)
-template <int KS, int QT, int QP>
-__device__ __forceinline__ void k3p_pairs(const h16x8 (&a)[2 * KS], const h16x8 *lq, unsigned msk, int t, float (&b1)[QT],
+// k3p_epi1 into query Q1 (sel) or Q0 of a pair: the query's state is selected with v_cndmask,
+// never a dynamically indexed register array, which would live in scratch (so Q0, Q1 are template
+// parameters: as run-time arguments they put 64-112 B of scratch per lane into every instance)
+template <int QT, int Q0, int Q1>
+__device__ __forceinline__ void k3p_epi_sel(const f32x16 &c, bool sel, int t, float (&b1)[QT], float (&b2)[QT], int (&i1)[QT]) {
+  float x1 = sel ? b1[Q1] : b1[Q0], x2 = sel ? b2[Q1] : b2[Q0];
+  int xi = sel ? i1[Q1] : i1[Q0];
+  k3p_epi1(c, t, x1, x2, xi);
+  b1[Q0] = sel ? b1[Q0] : x1;
+  b2[Q0] = sel ? b2[Q0] : x2;
+  i1[Q0] = sel ? i1[Q0] : xi;
+  b1[Q1] = sel ? x1 : b1[Q1];
+  b2[Q1] = sel ? x2 : b2[Q1];
+  i1[Q1] = sel ? xi : i1[Q1];
+}
+// query-tile pairs QP.. of one DB tile t over a view; msk's two bits of a pair = its need bits
+// (wave-uniform).  A pair with one needed tile runs one chain on it
+template <int KS, int QT, int QP, class V>
+__device__ __forceinline__ void k3p_pairs(const h16x8 (&a)[2 * KS], const V &v, unsigned msk, int t, float (&b1)[QT],
                                           float (&b2)[QT], int (&i1)[QT]) {
   if constexpr (2 * QP < QT) {
-    constexpr int NP = 2 * KS, q0 = 2 * QP, q1 = 2 * QP + 1;
+    constexpr int q0 = 2 * QP, q1 = 2 * QP + 1;
     const unsigned m2 = (msk >> q0) & 3u;
-    const h16x8 *qb0 = lq + q0 * NP * IA_WAVE;
     if constexpr (q1 < QT) {
       if (m2 == 3u) {
         f32x16 c0, c1;
-        k3p_chain2<KS>(a, qb0, qb0 + NP * IA_WAVE, c0, c1);
+        k3p_full2<KS>(a, v, q0, q1, c0, c1);
         k3h_epi2<QT>(c0, c1, q0, true, t, b1, b2, i1);
       } else if (m2 != 0u) {
         const bool sel = m2 == 2u;
-        const f32x16 c = k3p_chain<KS>(a, sel ? qb0 + NP * IA_WAVE : qb0);
-        float x1 = sel ? b1[q1] : b1[q0], x2 = sel ? b2[q1] : b2[q0];
-        int xi = sel ? i1[q1] : i1[q0];
-        k3p_epi1(c, t, x1, x2, xi);
-        b1[q0] = sel ? b1[q0] : x1;
-        b2[q0] = sel ? b2[q0] : x2;
-        i1[q0] = sel ? i1[q0] : xi;
-        b1[q1] = sel ? x1 : b1[q1];
-        b2[q1] = sel ? x2 : b2[q1];
-        i1[q1] = sel ? xi : i1[q1];
+        const f32x16 c = k3p_full<KS>(a, v, sel ? q1 : q0);
+        k3p_epi_sel<QT, q0, q1>(c, sel, t, b1, b2, i1);
       }
     } else {
       if (m2 == 1u) {
-        const f32x16 c = k3p_chain<KS>(a, qb0);
+        const f32x16 c = k3p_full<KS>(a, v, q0);
         k3p_epi1(c, t, b1[q0], b2[q0], i1[q0]);
       }
     }
-    k3p_pairs<KS, QT, QP + 1>(a, lq, msk, t, b1, b2, i1);
+    k3p_pairs<KS, QT, QP + 1>(a, v, msk, t, b1, b2, i1);
   }
 }
 
@@ -348,13 +391,6 @@ __device__ __forceinline__ void k3p_pairs(const h16x8 (&a)[2 * KS], const h16x8 
 // subnormal spacing 2^-25); lim_q takes twice the relative term.  A block that
 // fails the test holds only rows with |a - q|^2 > U'_q: they can neither be nor tie the NN, exactly
 // like the rows of a tile the box test skips, so the records stay certified.
-template <int KS>
-__device__ __forceinline__ f32x16 k3p_hh(const h16x8 (&a)[2 * KS], const h16x8 *qb) {
-  f32x16 c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < KS; s++) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], qb[(2 * s) * IA_WAVE], c, 0, 0, 0);
-  return c;
-}
 // (this file is built with -fno-honor-nans - no value here is ever NaN - so fminf / fmaxf are
 // single v_min3 / v_max3 instructions instead of a canonicalizing v_max_f32 x, x per operand
 // first; the MFMA read hazards stay the compiler's)
@@ -364,60 +400,39 @@ __device__ __forceinline__ float k3p_min16(const f32x16 &c) {
   const float m4 = fminf(fminf(c[12], c[13]), c[14]);
   return fminf(fminf(fminf(m0, m1), fminf(m2, m3)), fminf(m4, c[15]));
 }
-// k3p_variant 22: the same filter on a hi-only tile buffer (ld_hi); the blocks
-// that pass run their full chains one tile later, from the whole tile loaded only then
-template <int KS, int QT, int Q>
-__device__ __forceinline__ void k3p_hhpipe_h(const h16x8 (&h)[KS], const h16x8 *lq, unsigned msk, float rt,
-                                             const float *qzt, const float *qzw, f32x16 (&acc)[2], unsigned &pass) {
+// the test of a tile (R_t = rt): within(c, q) = some hi x hi value c of the tile's block with
+// query tile q can lie within its query's bound (wave-uniform).  qzt / qzw: z_q / w_q of this
+// lane's query of tile 0 (sorted slots, 32 per tile); the tile's term of lim_q is taken once
+__device__ __forceinline__ auto k3p_bound(float rt, const float *qzt, const float *qzw) {
+  const float rr = fmaf(rt, 0x1p-9f, 0x1p-20f);
+  return [=](const f32x16 &c, int q) -> bool {
+    const float lim = fmaf(rt, qzw[q * IA_TILE] + rr, qzt[q * IA_TILE]);
+    return __ballot(k3p_min16(c) <= lim) != 0ull;
+  };
+}
+// hi-only stream (k3p_variant 22): the filter on a hi-only tile buffer (ld_hi); the blocks that
+// pass run their full products one tile later, from the whole tile loaded only then.  Two
+// accumulators: block Q's products are issued before block Q - 1's test
+template <int KS, int QT, int Q, class B>
+__device__ __forceinline__ void k3p_hhpipe_h(const h16x8 (&h)[KS], const K3pQmixed<KS> &v, unsigned msk, const B &within,
+                                             f32x16 (&acc)[2], unsigned &pass) {
   if constexpr (Q <= QT) {
-    constexpr int NP = 2 * KS, QS = NP, PS = 2;
     if constexpr (Q < QT) {
-      if ((msk >> Q) & 1u) {
-        const h16x8 *qb = lq + Q * QS * IA_WAVE;
-        f32x16 c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        h16x8 qv[KS];  // the block's query pieces, all requested before the first product
-#pragma unroll
-        for (int s = 0; s < KS; s++) qv[s] = qb[(PS * s) * IA_WAVE];
-#pragma unroll
-        for (int s = 0; s < KS; s++) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(h[s], qv[s], c, 0, 0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, KS, 0);  // the KS LDS reads first (one wait),
-        __builtin_amdgcn_sched_group_barrier(0x008, KS, 0);  // then the KS products
-        acc[Q & 1] = c;
-      }
+      if ((msk >> Q) & 1u) acc[Q & 1] = k3p_hh<KS, true>(h, v, Q);
     }
     if constexpr (Q >= 1) {
-      if ((msk >> (Q - 1)) & 1u) {
-        const float lim = fmaf(rt, qzw[(Q - 1) * IA_TILE] + fmaf(rt, 0x1p-9f, 0x1p-20f), qzt[(Q - 1) * IA_TILE]);
-        pass |= __ballot(k3p_min16(acc[(Q - 1) & 1]) <= lim) != 0ull ? 1u << (Q - 1) : 0u;
-      }
+      if ((msk >> (Q - 1)) & 1u) pass |= within(acc[(Q - 1) & 1], Q - 1) ? 1u << (Q - 1) : 0u;
     }
-    k3p_hhpipe_h<KS, QT, Q + 1>(h, lq, msk, rt, qzt, qzw, acc, pass);
+    k3p_hhpipe_h<KS, QT, Q + 1>(h, v, msk, within, acc, pass);
   }
 }
-// k3p_variant 24 / 25: the same filter walking only the set bits of the need mask (a tile has
-// ≈ 2.7 of 11 blocks needed: the unrolled form spends its scalar instructions testing the other
-// bits).  Blocks in bit order, two accumulators: a block's products are issued before the
-// previous block's bound test, as in k3p_hhpipe_h; the query hi pieces at lq ([QT][KS][64]).
-template <int KS>
-__device__ __forceinline__ unsigned k3p_filter_bits(const h16x8 (&h)[KS], const h16x8 *lq, unsigned msk, float rt,
-                                                    const float *qzt, const float *qzw) {
-  const float rr = fmaf(rt, 0x1p-9f, 0x1p-20f);
-  auto prod = [&](int q) {
-    const h16x8 *qb = lq + q * KS * IA_WAVE;
-    f32x16 c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    h16x8 qv[KS];
-#pragma unroll
-    for (int s = 0; s < KS; s++) qv[s] = qb[s * IA_WAVE];
-#pragma unroll
-    for (int s = 0; s < KS; s++) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(h[s], qv[s], c, 0, 0, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, KS, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, KS, 0);
-    return c;
-  };
-  auto test = [&](const f32x16 &c, int q) -> unsigned {
-    const float lim = fmaf(rt, qzw[q * IA_TILE] + rr, qzt[q * IA_TILE]);
-    return __ballot(k3p_min16(c) <= lim) != 0ull ? 1u << q : 0u;
-  };
+// two passes (k3p_variant 24 / 25): the same filter walking only the set bits of the need mask (a
+// tile has ≈ 2.7 of 11 blocks needed: the unrolled form spends its scalar instructions testing the
+// other bits).  Blocks in bit order, two accumulators: a block's products are issued before the
+// previous block's test, as in k3p_hhpipe_h
+template <int KS, class B>
+__device__ __forceinline__ unsigned k3p_filter_bits(const h16x8 (&h)[KS], const K3pQsplit<KS> &v, unsigned msk, const B &within) {
+  auto test = [&](const f32x16 &c, int q) -> unsigned { return within(c, q) ? 1u << q : 0u; };
   unsigned pass = 0;
   f32x16 a0, a1;
   // a1 is read only after a product wrote it; without a definition here the compiler zeroes its
@@ -429,13 +444,13 @@ __device__ __forceinline__ unsigned k3p_filter_bits(const h16x8 (&h)[KS], const 
     if (!msk) break;
     qa = __builtin_ctz(msk);
     msk &= msk - 1;
-    a0 = prod(qa);
+    a0 = k3p_hh<KS, true>(h, v, qa);
     if (qb >= 0) pass |= test(a1, qb);
     qb = -1;
     if (!msk) break;
     qb = __builtin_ctz(msk);
     msk &= msk - 1;
-    a1 = prod(qb);
+    a1 = k3p_hh<KS, true>(h, v, qb);
     pass |= test(a0, qa);
     qa = -1;
   }
@@ -443,156 +458,53 @@ __device__ __forceinline__ unsigned k3p_filter_bits(const h16x8 (&h)[KS], const 
   if (qb >= 0) pass |= test(a1, qb);
   return pass;
 }
-
-// k3p_variant 24 / 25, second pass: the full 12-MFMA chains of a tile's filter-passing blocks
-// with the query hi pieces at qh ([QT][KS][64], LDS) and the lo pieces at ql (same layout, LDS):
-// the products and their order are k3p_chain's / k3p_chain2's, so values and records are v14's
-template <int KS>
-__device__ __forceinline__ f32x16 k3p_chain_hl(const h16x8 (&a)[2 * KS], const h16x8 *qh, const h16x8 *ql) {
-  f32x16 c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < KS; s++) {
-    const h16x8 xh = qh[s * IA_WAVE], xl = ql[s * IA_WAVE];
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], xh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], xl, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], xh, c, 0, 0, 0);
-  }
-  return c;
-}
-template <int KS>
-__device__ __forceinline__ void k3p_chain2_hl(const h16x8 (&a)[2 * KS], const h16x8 *qh0, const h16x8 *ql0, const h16x8 *qh1,
-                                              const h16x8 *ql1, f32x16 &c0, f32x16 &c1) {
-  constexpr f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  c0 = zero;
-  c1 = zero;
-#pragma unroll
-  for (int s = 0; s < KS; s++) {
-    const h16x8 x0h = qh0[s * IA_WAVE], x0l = ql0[s * IA_WAVE], x1h = qh1[s * IA_WAVE], x1l = ql1[s * IA_WAVE];
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], x0h, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], x1h, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], x0l, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], x1l, c1, 0, 0, 0);
-    c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], x0h, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], x1h, c1, 0, 0, 0);
-  }
-}
-// k3p_pairs with the query hi / lo pieces in separate LDS arrays (qh, ql: [QT][KS][64], lane offset
-// included)
-template <int KS, int QT, int QP>
-__device__ __forceinline__ void k3p_pairs_hl(const h16x8 (&a)[2 * KS], const h16x8 *qh, const h16x8 *ql, unsigned msk, int t,
-                                             float (&b1)[QT], float (&b2)[QT], int (&i1)[QT]) {
+// whole tiles (k3p_variant 20 / 21): the filter with fused corrections, organised like k3p_pairs -
+// the hi x hi chains of a query-tile pair run as two independent chains, both tests follow, and
+// the passing blocks' corrections run as two chains (both pass) or one, with the two-query
+// epilogue when both pass
+template <int KS, int QT, int QP, class V, class B>
+__device__ __forceinline__ void k3p_hhpairs(const h16x8 (&a)[2 * KS], const V &v, unsigned msk, const B &within, int t,
+                                            float (&b1)[QT], float (&b2)[QT], int (&i1)[QT], unsigned &pass) {
   if constexpr (2 * QP < QT) {
-    constexpr int QS = KS * IA_WAVE, q0 = 2 * QP, q1 = 2 * QP + 1;
+    constexpr int q0 = 2 * QP, q1 = 2 * QP + 1;
     const unsigned m2 = (msk >> q0) & 3u;
     if constexpr (q1 < QT) {
       if (m2 == 3u) {
-        f32x16 c0, c1;
-        k3p_chain2_hl<KS>(a, qh + q0 * QS, ql + q0 * QS, qh + q1 * QS, ql + q1 * QS, c0, c1);
-        k3h_epi2<QT>(c0, c1, q0, true, t, b1, b2, i1);
-      } else if (m2 != 0u) {
-        const bool sel = m2 == 2u;
-        const int qq = sel ? q1 : q0;
-        const f32x16 c = k3p_chain_hl<KS>(a, qh + qq * QS, ql + qq * QS);
-        float x1 = sel ? b1[q1] : b1[q0], x2 = sel ? b2[q1] : b2[q0];
-        int xi = sel ? i1[q1] : i1[q0];
-        k3p_epi1(c, t, x1, x2, xi);
-        b1[q0] = sel ? b1[q0] : x1;
-        b2[q0] = sel ? b2[q0] : x2;
-        i1[q0] = sel ? i1[q0] : xi;
-        b1[q1] = sel ? x1 : b1[q1];
-        b2[q1] = sel ? x2 : b2[q1];
-        i1[q1] = sel ? xi : i1[q1];
-      }
-    } else {
-      if (m2 == 1u) {
-        const f32x16 c = k3p_chain_hl<KS>(a, qh + q0 * QS, ql + q0 * QS);
-        k3p_epi1(c, t, b1[q0], b2[q0], i1[q0]);
-      }
-    }
-    k3p_pairs_hl<KS, QT, QP + 1>(a, qh, ql, msk, t, b1, b2, i1);
-  }
-}
-
-// k3p_variant 20 / 21: the filter with fused corrections, organised like k3p_pairs - the
-// hi x hi chains of a query-tile pair run as two independent chains, both bound tests follow,
-// and the passing blocks' corrections run as two chains (both pass) or one, with the two-query
-// epilogue when both pass.  Two independent MFMA chains per pair instead of k3p_hhfuse's
-// software pipeline over single chains.
-template <int KS>
-__device__ __forceinline__ void k3p_corr(const h16x8 (&a)[2 * KS], const h16x8 *qb, f32x16 &c) {
-#pragma unroll
-  for (int s = 0; s < KS; s++) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], qb[(2 * s) * IA_WAVE], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], qb[(2 * s + 1) * IA_WAVE], c, 0, 0, 0);
-  }
-}
-template <int KS, int QT, int QP>
-__device__ __forceinline__ void k3p_hhpairs(const h16x8 (&a)[2 * KS], const h16x8 *lq, unsigned msk, float rt,
-                                            const float *qzt, const float *qzw, int t, float (&b1)[QT], float (&b2)[QT],
-                                            int (&i1)[QT], unsigned &pass) {
-  if constexpr (2 * QP < QT) {
-    constexpr int NP = 2 * KS, q0 = 2 * QP, q1 = 2 * QP + 1;
-    const unsigned m2 = (msk >> q0) & 3u;
-    const h16x8 *qb0 = lq + q0 * NP * IA_WAVE, *qb1 = qb0 + NP * IA_WAVE;
-    const float rr = fmaf(rt, 0x1p-9f, 0x1p-20f);
-    if constexpr (q1 < QT) {
-      if (m2 == 3u) {
-        constexpr f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        f32x16 c0 = zero, c1 = zero;
-#pragma unroll
-        for (int s = 0; s < KS; s++) {
-          c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], qb0[(2 * s) * IA_WAVE], c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], qb1[(2 * s) * IA_WAVE], c1, 0, 0, 0);
-        }
-        const bool p0 = __ballot(k3p_min16(c0) <= fmaf(rt, qzw[q0 * IA_TILE] + rr, qzt[q0 * IA_TILE])) != 0ull;
-        const bool p1 = __ballot(k3p_min16(c1) <= fmaf(rt, qzw[q1 * IA_TILE] + rr, qzt[q1 * IA_TILE])) != 0ull;
+        f32x16 c0 = k3p_hh<KS, false>(a, v, q0), c1 = k3p_hh<KS, false>(a, v, q1);
+        const bool p0 = within(c0, q0), p1 = within(c1, q1);
         pass |= (p0 ? 1u << q0 : 0u) | (p1 ? 1u << q1 : 0u);
         if (p0 && p1) {
-#pragma unroll
-          for (int s = 0; s < KS; s++) {
-            c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], qb0[(2 * s) * IA_WAVE], c0, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s + 1], qb1[(2 * s) * IA_WAVE], c1, 0, 0, 0);
-            c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], qb0[(2 * s + 1) * IA_WAVE], c0, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * s], qb1[(2 * s + 1) * IA_WAVE], c1, 0, 0, 0);
-          }
+          k3p_corr<KS>(a, v, q0, c0);
+          k3p_corr<KS>(a, v, q1, c1);
           k3h_epi2<QT>(c0, c1, q0, true, t, b1, b2, i1);
         } else if (p0) {
-          k3p_corr<KS>(a, qb0, c0);
+          k3p_corr<KS>(a, v, q0, c0);
           k3p_epi1(c0, t, b1[q0], b2[q0], i1[q0]);
         } else if (p1) {
-          k3p_corr<KS>(a, qb1, c1);
+          k3p_corr<KS>(a, v, q1, c1);
           k3p_epi1(c1, t, b1[q1], b2[q1], i1[q1]);
         }
       } else if (m2 != 0u) {
         const bool sel = m2 == 2u;
-        const h16x8 *qb = sel ? qb1 : qb0;
-        f32x16 c = k3p_hh<KS>(a, qb);
         const int qq = sel ? q1 : q0;
-        if (__ballot(k3p_min16(c) <= fmaf(rt, qzw[qq * IA_TILE] + rr, qzt[qq * IA_TILE])) != 0ull) {
+        f32x16 c = k3p_hh<KS, false>(a, v, qq);
+        if (within(c, qq)) {
           pass |= 1u << qq;
-          k3p_corr<KS>(a, qb, c);
-          float x1 = sel ? b1[q1] : b1[q0], x2 = sel ? b2[q1] : b2[q0];
-          int xi = sel ? i1[q1] : i1[q0];
-          k3p_epi1(c, t, x1, x2, xi);
-          b1[q0] = sel ? b1[q0] : x1;
-          b2[q0] = sel ? b2[q0] : x2;
-          i1[q0] = sel ? i1[q0] : xi;
-          b1[q1] = sel ? x1 : b1[q1];
-          b2[q1] = sel ? x2 : b2[q1];
-          i1[q1] = sel ? xi : i1[q1];
+          k3p_corr<KS>(a, v, qq, c);
+          k3p_epi_sel<QT, q0, q1>(c, sel, t, b1, b2, i1);
         }
       }
     } else {
       if (m2 == 1u) {
-        f32x16 c = k3p_hh<KS>(a, qb0);
-        if (__ballot(k3p_min16(c) <= fmaf(rt, qzw[q0 * IA_TILE] + rr, qzt[q0 * IA_TILE])) != 0ull) {
+        f32x16 c = k3p_hh<KS, false>(a, v, q0);
+        if (within(c, q0)) {
           pass |= 1u << q0;
-          k3p_corr<KS>(a, qb0, c);
+          k3p_corr<KS>(a, v, q0, c);
           k3p_epi1(c, t, b1[q0], b2[q0], i1[q0]);
         }
       }
     }
-    k3p_hhpairs<KS, QT, QP + 1>(a, lq, msk, rt, qzt, qzw, t, b1, b2, i1, pass);
+    k3p_hhpairs<KS, QT, QP + 1>(a, v, msk, within, t, b1, b2, i1, pass);
   }
 }
 
@@ -937,6 +849,16 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
   spec_hi();
 
   // ---- front end, in-kernel sort: sort, scatter to sorted slots; query-tile boxes
+  auto to_slot = [=](int rank) {  // this thread's query to its sorted slot, when this launch holds it
+    const int x = rank - s0;
+    if (x >= 0 && x < NQ) {
+      qlo[x] = mlo;
+      qhi[x] = mhi;
+      qU[x] = mU;
+      qzt[x] = mzt;
+      qzw[x] = mzw;
+    }
+  };
   if (Mpad > IA_K3P_RANK_MAX) {  // (uniform) up to IA_K3P_RANK_MAX queries the rank count
     // bitonic network over the first 512 threads' unique keys (padding: 0xFFFFFFFF, last):
     // exchanges at distance < 64 are lane swaps, the 6 at distance >= 64 go through LDS (the
@@ -968,16 +890,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       rankof[q] = tid;
     }
     __syncthreads();
-    if (tid < Mpad) {
-      const int x = rankof[tid] - s0;
-      if (x >= 0 && x < NQ) {
-        qlo[x] = mlo;
-        qhi[x] = mhi;
-        qU[x] = mU;
-        qzt[x] = mzt;
-        qzw[x] = mzw;
-      }
-    }
+    if (tid < Mpad) to_slot(rankof[tid]);
   } else if (tid < Mpad) {
     int rank = 0;
     for (int j = 0; j < Mpad; j += 4) {
@@ -986,14 +899,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     }
     order[rank] = tid;
     rankof[tid] = rank;
-    const int x = rank - s0;
-    if (x >= 0 && x < NQ) {
-      qlo[x] = mlo;
-      qhi[x] = mhi;
-      qU[x] = mU;
-      qzt[x] = mzt;
-      qzw[x] = mzw;
-    }
+    to_slot(rank);
   }
   [[maybe_unused]] unsigned long long pa = 0, pb = 0, pc = 0;  // (phase probe stamps)
   K3P_T(pa);
@@ -1080,14 +986,14 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     // ---- tile walk, two passes (k3p_variant 24 / 25) over the workgroup's tiles.
     // (a) the hi stream: the hi halves (3.5 of 7 KiB per tile at KS = 4) by LDS-DMA into the
     //     wave's ring of three LDS slots, two tiles in flight while the third is filtered: per tile
-    //     the hi x hi filter of its box-needed blocks (k3p_hhpipe_h on the slot); a tile with a
+    //     the hi x hi filter of its box-needed blocks (k3p_filter_bits on the slot); a tile with a
     //     passing block goes to a list in LDS.  The loop issues no other vector-memory instruction
     //     (need tests, the tile counter and the list are LDS / VALU work) and exactly four DMAs per
     //     tile (past the last needed tile the same four from the wave's last tile, into the slot
     //     that is never read), so "vmcnt(8)" before a slot is read waits for that slot alone.
     // (b) after a barrier the query lo pieces are staged into the ring area and the listed tiles
     //     are handed out through an LDS counter: whole tiles (two register buffers) and the full
-    //     12-MFMA chains of their passing blocks (k3p_pairs_hl: v14's products and records).
+    //     12-MFMA chains of their passing blocks (k3p_pairs over the split view: k3p_full's products).
     // Tiles: wave w's first two are w and w + NW (the speculative DMAs issued before the query
     // sort), the others come from the workgroup's LDS counter; the passing tiles go to one list
     // (plk / plm, LDS atomic).  The DMAs are inline asm, which the compiler does not track, so it
@@ -1179,7 +1085,9 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       if (mc) {  // wave-uniform (0: a speculative tile that is not needed)
         h16x8 hc[KS];
         slot_hi(hc, wring + sl * IA_HSLOT, lane);
-        const unsigned pass = k3p_filter_bits<KS>(hc, ldsh + lane, mc, wR[kc], qzt + (lane & 31), qzw + (lane & 31));
+        // (no lo pieces yet: their area holds the rings)
+        const unsigned pass = k3p_filter_bits<KS>(hc, K3pQsplit<KS>{ldsh + lane, nullptr}, mc,
+                                                  k3p_bound(wR[kc], qzt + (lane & 31), qzw + (lane & 31)));
         cnt += __popc(mc);
         if (pass) {  // wave-uniform
           nfull += __popc(pass);
@@ -1262,7 +1170,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       ld_tile<KS>(nxt, db, tk(kn >= 0 ? kn : kcur), lane);  // unconditional (equal vmcnt)
       const int prow = pos2row[(int64_t)tk(kcur) * IA_TILE + (lane & 31)];
       asm volatile("" ::: "memory");
-      k3p_pairs_hl<KS, QT, 0>(cur, ldsh + lane, qlo_f + lane, mcur, kcur, b1, b2, i1);  // i1: the WG-local tile
+      k3p_pairs<KS, QT, 0>(cur, K3pQsplit<KS>{ldsh + lane, qlo_f + lane}, mcur, kcur, b1, b2, i1);  // i1: the WG-local tile
       if (lane < 32) rowmap[kcur * IA_TILE + lane] = prow;
       kcur = kn;
       mcur = mn;
@@ -1282,6 +1190,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     }
 #endif
     } else {
+    const K3pQmixed<KS> qv{ldsh + lane};
     unsigned m;
     int k = next_k(wave, m);
     if constexpr (FORM == K3pStream::HiOnly) {
@@ -1290,7 +1199,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
     // rotation, the next tile's in flight); the tile's lo halves are then loaded only when a
     // block passed (its hi halves copied from the hi buffer; else the same load instructions at
     // one lane-uniform address: equal outstanding loads on every path) and its full chains
-    // (k3p_pairs: v14's products and records) run one tile later, while the next tile is
+    // (k3p_pairs: k3p_full's products) run one tile later, while the next tile is
     // filtered.  MALL / HBM bytes: hi of every needed tile + lo of the passing ones (15 % of the
     // loaded tiles at cfg3 with option nn_bound, 46 % without).
     h16x8 ha[KS], hb[KS];
@@ -1305,8 +1214,8 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       asm volatile("" ::: "memory");  // LDS query fragments are re-read per tile, not hoisted
       f32x16 acc[2];
       unsigned pass = 0;
-      k3p_hhpipe_h<KS, QT, 0>(cur, ldsh + lane, m, wR[k], qzt + (lane & 31), qzw + (lane & 31), acc, pass);
-      if (pprev) k3p_pairs<KS, QT, 0>(a, ldsh + lane, pprev, tk(kprev), b1, b2, i1);
+      k3p_hhpipe_h<KS, QT, 0>(cur, qv, m, k3p_bound(wR[k], qzt + (lane & 31), qzw + (lane & 31)), acc, pass);
+      if (pprev) k3p_pairs<KS, QT, 0>(a, qv, pprev, tk(kprev), b1, b2, i1);
       {
         // a passing tile: its lo pieces (the hi ones are copied from cur); otherwise the same
         // instructions at one lane-uniform address (one request each, no bytes streamed), so
@@ -1333,7 +1242,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       if (k >= K) break;
       step3(hb, ha);
     }
-    if (pprev) k3p_pairs<KS, QT, 0>(a, ldsh + lane, pprev, tk(kprev), b1, b2, i1);
+    if (pprev) k3p_pairs<KS, QT, 0>(a, qv, pprev, tk(kprev), b1, b2, i1);
     } else {
     // (re)load the first needed tile unconditionally (usually the speculative one again: a
     // cache hit), so the loop is entered with the same outstanding loads on every path
@@ -1348,7 +1257,7 @@ k3h_prune3(const h16x8 *__restrict__ db, const h16x8 *__restrict__ qf, const flo
       asm volatile("" ::: "memory");  // LDS query fragments are re-read per tile, not hoisted
       {  // the fused corrections on query-tile pairs
         unsigned pass = 0;
-        k3p_hhpairs<KS, QT, 0>(cur, ldsh + lane, m, wR[k], qzt + (lane & 31), qzw + (lane & 31), tk(k), b1, b2, i1, pass);
+        k3p_hhpairs<KS, QT, 0>(cur, qv, m, k3p_bound(wR[k], qzt + (lane & 31), qzw + (lane & 31)), tk(k), b1, b2, i1, pass);
         nfull += __popc(pass);
         ntp += pass != 0u;
       }
@@ -1504,10 +1413,10 @@ void ia_k3p_probe_dump() {  // diagnostic build only: phase cycles per plateau w
           (double)v[13] / v[4], (double)v[14] / v[4], (double)v[15] / v[4]);
   fprintf(stderr, "K3P_PROBE tail split: half merge %.0f, barrier %.0f, subset merge + records %.0f\n", (double)v[9] / v[4],
           (double)v[10] / v[4], (double)v[11] / v[4]);
-  fprintf(stderr, "K3P_PROBE v3 phases if variant>=3: load=setup, sort+scatter=need, need=loop, loop=tail, tail=[7]\n");
-  fprintf(stderr, "K3P_PROBE [7]=%.0f [8]=%.0f ([8] = the tail barrier wait)\n", (double)v[7] / v[4],
+  fprintf(stderr, "K3P_PROBE tail %.0f, of which the barrier wait for the slowest wave %.0f\n", (double)v[7] / v[4],
           (double)v[8] / v[4]);
-  fprintf(stderr, "K3P_PROBE waves=%llu setup=%.0f need=%.0f loop=%.0f tail=%.0f tiles/wave=%.2f pairs/wave=%.2f (cycles/wave)\n",
+  fprintf(stderr, "K3P_PROBE waves=%llu input wait + loads=%.0f sort + scatter=%.0f state init=%.0f tile walk=%.0f "
+                  "tiles/wave=%.2f pairs/wave=%.2f (cycles/wave)\n",
           v[4], (double)v[0] / v[4], (double)v[1] / v[4], (double)v[2] / v[4], (double)v[3] / v[4], (double)v[5] / v[4],
           (double)v[6] / v[4]);
   unsigned long long z[24] = {};

@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(PR_WG) k_tile_boxes(const int *__restrict__ po
     lo[i] = DBL_MAX;
     hi[i] = -DBL_MAX;
   }
-  float rt = 0.f;  // R_t = max |a'| over the tile's real rows (K3p's hi x hi filter, k3p_variant 14/15)
+  float rt = 0.f;  // R_t = max |a'| over the tile's real rows (K3p's hi x hi filter, ia_k3h.hip k3p_bound)
   for (int j = 0; j < IA_TILE; j++) {
     const int row = pos2row[(int64_t)t * IA_TILE + j];
     if (row >= NA) continue;
@@ -183,7 +183,7 @@ __global__ void __launch_bounds__(PR_WG) k_tile_boxes(const int *__restrict__ po
   tnorm[t] = rt;
 }
 
-// K2s: one sort of a wavefront step's queries for the pruned scan (k3p_variant 11).  One
+// K2s: one sort of a wavefront step's queries for the presorted pruned scan (k3p_variant 21 / 25).  One
 // workgroup per sorted query tile: each sorts the step's unique keys (the Morton key's top 20
 // bits above the 12-bit query index; padding slots and unused sort slots last) by a bitonic
 // network in LDS - the same order in every workgroup - and writes its tile's pruning records,

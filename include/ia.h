@@ -73,12 +73,11 @@ typedef struct {
                              * compute_distance's `** 2` (libm pow on a numpy scalar) rounded a
                              * near-midpoint square the other way than y * y does (audit; no
                              * fixture has one) */
-  double dist_pairs_corrected; /* k3p_variant 14/15: pairs whose hi x hi value passed the bound
-                                * (correction products + top-2 epilogue run); 16/17: pairs whose
-                                * head (15-axis partial distance) passed; else 0 */
-  double dist_tiles_rows;   /* hi x hi block filter (k3p_variant 14, 15, 18..21): loaded DB tiles with
-                             * at least one block passing the filter (the only ones whose lo halves
-                             * the correction products read) */
+  double dist_pairs_corrected; /* the pruned scan's hi x hi block filter (ia_k3h.hip, k3p_bound):
+                                * pairs whose hi x hi value passed the bound (correction products +
+                                * top-2 epilogue run); 0 without the pruned scan */
+  double dist_tiles_rows;   /* the same filter: loaded DB tiles with at least one block passing it
+                             * (the only ones whose lo halves the correction products read) */
   /* feature-gather kernels (bench.py roofline.gathers; DESIGN.md §4 algorithmic bytes) */
   double k1b_ms;            /* K1b k_db64_build (fp64 row DB), device ms summed over the levels */
   double k1b_bytes;         /* its algorithmic bytes: A-side images read once + N_A rows written */

@@ -30,16 +30,17 @@ SETTINGS = {
     'pruned_v25': dict(PRUNED, k3p_variant=25),
     'pruned_v22': dict(PRUNED, k3p_variant=22),
     'pruned_v21': dict(PRUNED, k3p_variant=21),
+    'pruned_v20': dict(PRUNED, k3p_variant=20),
     'pruned_min_rows_1': dict(PRUNED),
     # several DB tiles per workgroup: 259 tiles on 64 workgroups
     'pruned_v24_wgs64': dict(PRUNED, k3p_variant=24, scan_wgs=64),
     # 259 tiles >= 64 * 2: the level shards (debug records are single-rank only: s, im and B' are checked)
     'pruned_shard2': dict(PRUNED, shard_emulate=2),
 }
-SIX = ['default', 'f32', 'pruned_v24', 'pruned_v25', 'pruned_v22', 'pruned_v21']
-RUNS = ([(c, s) for c in AI.BASE_CASES for s in SIX] +
+PATHS = ['default', 'f32', 'pruned_v24', 'pruned_v25', 'pruned_v22', 'pruned_v21', 'pruned_v20']
+RUNS = ([(c, s) for c in AI.BASE_CASES for s in PATHS] +
         [('k0', s) for s in ('default', 'f32', 'pruned_v24')] +
-        [(c, s) for c in AI.BIG_CASES for s in SIX + ['pruned_v24_wgs64', 'pruned_shard2']] +
+        [(c, s) for c in AI.BIG_CASES for s in PATHS + ['pruned_v24_wgs64', 'pruned_shard2']] +
         [(c, s) for c in AI.GATE_CASES for s in ('default', 'pruned_min_rows_1')])
 
 
