@@ -10,3 +10,5 @@ libia.so through a ctypes C ABI (include/ia.h).  Import as `ia_amd` (see ia_amd.
 root, which maps this hyphenated directory to that package name).
 """
 __version__ = '0.1.0'
+
+from .img_preprocess import augment_pairs  # noqa: E402,F401  (ia_amd.augment_pairs)

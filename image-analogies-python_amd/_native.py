@@ -22,6 +22,10 @@ class IAError(RuntimeError):
     pass
 
 
+class IAShapeError(IAError, ValueError):
+    """A list of A images that does not pair up with the A' images (count or shape)."""
+
+
 class LevelArgs(ctypes.Structure):
     _fields_ = [('ch', ctypes.c_int), ('n_ap', ctypes.c_int), ('a_h', ctypes.c_int), ('a_w', ctypes.c_int),
                 ('b_h', ctypes.c_int), ('b_w', ctypes.c_int),
@@ -29,7 +33,7 @@ class LevelArgs(ctypes.Structure):
                 ('B', ctypes.c_void_p), ('Bc', ctypes.c_void_p), ('Bpc', ctypes.c_void_p), ('Bp', ctypes.c_void_p),
                 ('weights', ctypes.c_void_p), ('kappa_factor', ctypes.c_double),
                 ('s_out', ctypes.c_void_p), ('im_out', ctypes.c_void_p), ('mem', ctypes.c_int),
-                ('dbg_src', ctypes.c_void_p), ('dbg_dist', ctypes.c_void_p)]
+                ('dbg_src', ctypes.c_void_p), ('dbg_dist', ctypes.c_void_p), ('n_a', ctypes.c_int)]
 
 
 class Stats(ctypes.Structure):
@@ -174,6 +178,29 @@ def _c64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def is_pair_list(A):
+    """An A side given as a list or tuple holds one image per A' (training pairs (A_i, A'_i));
+    a single array is the one A every A' shares (the reference, algorithms.py:63-67)."""
+    return isinstance(A, (list, tuple))
+
+
+def stack_pairs(A_list, Ac_list, n_ap):
+    """The A / Ac images of n_ap pairs as the two stacked arrays ia_level_args takes (n_a = n_ap).
+    Pairs of different sizes would need a per-image row codec (DB row = img * h * w + r * w + c):
+    they are refused, as is a list that has not one A per A'."""
+    if not (is_pair_list(A_list) and is_pair_list(Ac_list)):
+        raise IAShapeError('A and Ac must both be lists (one image per A\') or both single arrays')
+    if len(A_list) != n_ap or len(Ac_list) != n_ap:
+        raise IAShapeError("a list of A images needs one A and one Ac per A' image: %d A, %d Ac, %d A'"
+                           % (len(A_list), len(Ac_list), n_ap))
+    A_list, Ac_list = [_c64(x) for x in A_list], [_c64(x) for x in Ac_list]
+    for name, xs in (('A', A_list), ('Ac', Ac_list)):
+        if any(x.shape != xs[0].shape for x in xs):
+            raise IAShapeError('every %s of a pair list must have one shape (got %s); pairs of different sizes '
+                               'are not supported' % (name, [x.shape for x in xs]))
+    return _c64(np.stack(A_list)), _c64(np.stack(Ac_list))
+
+
 def check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w):
     """The C ABI derives every size from A's channel count and B's shape (include/ia.h
     ia_level_args); check the rest here so a mismatched call raises instead of reading or
@@ -301,7 +328,9 @@ class Context(object):
 
     def synthesize_level(self, A, Ac, Ap_list, Apc_list, B, Bc, Bpc, Bp, weights, kappa_factor, stats=None,
                          debug=None):
-        """ia_synthesize_level on host numpy arrays.  Bp (fp64, C-contiguous) is updated in place
+        """ia_synthesize_level on host numpy arrays.  A / Ac: one array each (the A every A' shares)
+        or lists with one array per A' (pairs (A_i, A'_i) of equal shape; IAShapeError, a
+        ValueError, otherwise).  Bp (fp64, C-contiguous) is updated in place
         (the reference mutates Bp_pyr[level], image_analogies.py:214).  Returns (s, im):
         s (N, 2) int32 source pixel in A', im (N,) int32 source A' image, raster order.
         debug: a dict to receive the debug=True per-pixel records (include/ia.h dbg_src/dbg_dist):
@@ -314,13 +343,20 @@ class Context(object):
         """ia_synthesize_levels: one level of several jobs that share the A side (A, A' levels l and
         l-1), e.g. a kappa / pyramid-depth sweep (multi_script.py).  jobs: list of dicts with
         B, Bc, Bpc, Bp (updated in place), weights, kappa_factor and optionally debug (a dict, see
-        synthesize_level).  One DB, one distance scan per wavefront step for all jobs.  Returns
+        synthesize_level).  A / Ac may be lists, one image per A' (pairs), as in synthesize_level.
+        One DB, one distance scan per wavefront step for all jobs.  Returns
         [(s, im)] per job, each identical to a separate synthesize_level call."""
         if not 1 <= len(jobs) <= 32:
             raise IAError('synthesize_levels: 1..32 jobs per call (got %d)' % len(jobs))
-        A, Ac = _c64(A), _c64(Ac)
         Ap = _c64(np.stack(Ap_list))
         Apc = _c64(np.stack(Apc_list))
+        n_a = 0
+        if is_pair_list(A) or is_pair_list(Ac):
+            A_all, Ac_all = stack_pairs(A, Ac, Ap.shape[0])   # (n_a, h, w[, ch]): what the library reads
+            A, Ac, n_a = A_all[0], Ac_all[0], Ap.shape[0]     # one image: what the shapes are checked on
+        else:
+            A, Ac = _c64(A), _c64(Ac)
+            A_all, Ac_all = A, Ac
         keep, args, outs = [], [], []
         for jb in jobs:
             B, Bc, Bpc, Bp, w = _c64(jb['B']), _c64(jb['Bc']), _c64(jb['Bpc']), jb['Bp'], _c64(jb['weights'])
@@ -335,9 +371,9 @@ class Context(object):
                 dsrc = np.zeros((bh * bw, 6), dtype=np.int32)
                 ddist = np.zeros((bh * bw, 2), dtype=np.float64)
             args.append(LevelArgs(ch, Ap.shape[0], A.shape[0], A.shape[1], bh, bw,
-                                  _ptr(A), _ptr(Ac), _ptr(Ap), _ptr(Apc), _ptr(B), _ptr(Bc), _ptr(Bpc), _ptr(Bp),
+                                  _ptr(A_all), _ptr(Ac_all), _ptr(Ap), _ptr(Apc), _ptr(B), _ptr(Bc), _ptr(Bpc), _ptr(Bp),
                                   _ptr(w), float(jb['kappa_factor']), _ptr(s), _ptr(im), IA_MEM_HOST,
-                                  None if dsrc is None else _ptr(dsrc), None if ddist is None else _ptr(ddist)))
+                                  None if dsrc is None else _ptr(dsrc), None if ddist is None else _ptr(ddist), n_a))
             keep.append((B, Bc, Bpc, w))
             outs.append((s, im, dsrc, ddist, jb.get('debug')))
         arr = (LevelArgs * len(args))(*args)
@@ -355,20 +391,23 @@ class Context(object):
             res.append((s, im))
         return res
 
-    def synthesize_level_device(self, ch, n_ap, a_hw, b_hw, ptrs, kappa_factor, stats=None):
+    def synthesize_level_device(self, ch, n_ap, a_hw, b_hw, ptrs, kappa_factor, stats=None, n_a=0):
         """Same on device pointers (IA_MEM_DEVICE): ptrs = dict of int addresses for
-        A, Ac, Ap, Apc, B, Bc, Bpc, Bp, weights, s_out, im_out (e.g. torch tensor data_ptr())."""
-        return self.synthesize_levels_device(ch, n_ap, a_hw, b_hw, [ptrs], [kappa_factor], stats)
+        A, Ac, Ap, Apc, B, Bc, Bpc, Bp, weights, s_out, im_out (e.g. torch tensor data_ptr()).
+        n_a = n_ap: A and Ac stack one image per A' (pairs); 0 or 1: one shared A."""
+        return self.synthesize_levels_device(ch, n_ap, a_hw, b_hw, [ptrs], [kappa_factor], stats, n_a=n_a)
 
-    def synthesize_levels_device(self, ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, stats=None):
+    def synthesize_levels_device(self, ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, stats=None, n_a=0):
         """ia_synthesize_levels on device pointers: one ptrs dict per job (the A-side addresses
-        must be equal in all of them), one kappa factor per job."""
+        must be equal in all of them), one kappa factor per job; n_a as in synthesize_level_device,
+        or a list with one value per job (the library refuses jobs that differ)."""
         args = []
-        for ptrs, kf in zip(ptr_list, kappa_factors):
+        n_as = list(n_a) if isinstance(n_a, (list, tuple)) else [n_a] * len(ptr_list)
+        for ptrs, kf, na in zip(ptr_list, kappa_factors, n_as):
             p = {k: ctypes.c_void_p(int(v)) for k, v in ptrs.items()}
             args.append(LevelArgs(ch, n_ap, a_hw[0], a_hw[1], b_hw[0], b_hw[1], p['A'], p['Ac'], p['Ap'], p['Apc'],
                                   p['B'], p['Bc'], p['Bpc'], p['Bp'], p['weights'], float(kf),
-                                  p['s_out'], p['im_out'], IA_MEM_DEVICE))
+                                  p['s_out'], p['im_out'], IA_MEM_DEVICE, None, None, int(na)))
         arr = (LevelArgs * len(args))(*args)
         st = stats if stats is not None else Stats()
         check(lib().ia_synthesize_levels(self._h, arr, len(args), ctypes.byref(st)), 'ia_synthesize_levels')

@@ -35,6 +35,18 @@ def default_context():
     return _CTX
 
 
+def is_pyramid_list(A_pyr):
+    """The A side of the level loop is one pyramid (a list of level arrays: the A every A' shares)
+    or a list of pyramids, one per A' (pairs (A_i, A'_i)): the one whose first element is itself a
+    list or tuple."""
+    return len(A_pyr) > 0 and isinstance(A_pyr[0], (list, tuple))
+
+
+def a_levels(A_pyr, level):
+    """A_pyr's level as Context.synthesize_level takes it: one array, or one array per pair."""
+    return [p[level] for p in A_pyr] if is_pyramid_list(A_pyr) else A_pyr[level]
+
+
 def _reflect(i, n):
     i = np.asarray(i) % (2 * n)
     return np.where(i >= n, 2 * n - 1 - i, i)
@@ -144,16 +156,24 @@ def _rows_index(As):
 
 def create_index(A_pyr, Ap_pyr_list, c):
     """Per-level DB of [A full feature | A'_i half feature] rows stacked over the A' images and
-    its (GPU) index (algorithms.py:50-70).  Returns (flann, flann_params, As, As_size)."""
-    A_feat = compute_feature_array(A_pyr, c, full_feat=True)
+    its (GPU) index (algorithms.py:50-70).  Returns (flann, flann_params, As, As_size).
+    A_pyr may be a list of pyramids, one per A' (is_pyramid_list): image i's rows are then
+    [A_i full feature | A'_i half feature]."""
     Ap_feats = [compute_feature_array(p, c, full_feat=False) for p in Ap_pyr_list]
+    if is_pyramid_list(A_pyr):
+        if len(A_pyr) != len(Ap_pyr_list):
+            raise ValueError("a list of A pyramids needs one per A' pyramid (got %d for %d)"
+                             % (len(A_pyr), len(Ap_pyr_list)))
+        A_feats = [compute_feature_array(p, c, full_feat=True) for p in A_pyr]
+    else:
+        A_feats = [compute_feature_array(A_pyr, c, full_feat=True)] * len(Ap_feats)
     L = c.max_levels
     flann = [GpuFLANN() for _ in range(L)]
     flann_params = [[] for _ in range(L)]
     As = [[] for _ in range(L)]
     As_size = [[] for _ in range(L)]
     for level in range(1, L):
-        As[level] = np.vstack([np.hstack([A_feat[level], f[level]]) for f in Ap_feats])
+        As[level] = np.vstack([np.hstack([a[level], f[level]]) for a, f in zip(A_feats, Ap_feats)])
         As_size[level] = As[level].shape
         flann_params[level] = flann[level].build_index(As[level], algorithm='kdtree')
         As[level] = IndexedRows(As[level], flann[level]._index)

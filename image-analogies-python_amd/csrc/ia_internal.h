@@ -60,7 +60,8 @@ struct LevelGeo {
   int n_tiles;              // ceil(NA / 32) over the whole DB
   int tile0, tile1;         // this rank's shard [tile0, tile1)
   int tiles_per_wg, nwg;    // distance-kernel decomposition of the shard
-  const int *pos2row;       // pruned levels: position -> row table (ia_prune.hip); nullptr: ia_pos_row
+  int n_a;                  // A images: 1 (one A shared by every A') or n_ap (pairs (A_i, A'_i))
+  const int *pos2row;      // pruned levels: position -> row table (ia_prune.hip); nullptr: ia_pos_row
 };
 
 struct Imgs {        // the four pyramid images a feature row reads (see FeatDesc parts)
@@ -71,6 +72,20 @@ struct Imgs {        // the four pyramid images a feature row reads (see FeatDes
   int h, w, hc, wc;  // fine / coarse dims
   int64_t img_stride_f, img_stride_c;  // per-A'-image strides (0 for B')
 };
+// Per-image strides of p0 / p1 on the A side: 0 when every A' shares one A, the image sizes when
+// the level holds pairs (A_i, A'_i).  Only the DB builders (ia_level_db.hip) read the A images, so
+// the strides travel as their own argument and Imgs - an argument of every gather and merge on
+// the query path - keeps its size.
+struct APairs {
+  int64_t stride_f, stride_c;
+  int n_a;  // images parts 0 and 1 are averaged over (K0)
+};
+// the A side as image `img`'s rows read it
+__host__ __device__ inline Imgs ia_pair_imgs(Imgs A, const APairs &ap, int img) {
+  A.p0 += img * ap.stride_c;
+  A.p1 += img * ap.stride_f;
+  return A;
+}
 
 struct MergeArgs {
   const double *db64;  // fp64 row-major feature DB of the level (K1b), stride ia_db64_stride(ch)

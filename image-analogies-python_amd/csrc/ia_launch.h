@@ -10,8 +10,10 @@
 
 // allow a kernel the whole LDS of a CU as dynamic shared memory (once per kernel; thread-safe)
 void ia_allow_full_lds(const void *fn);
-void ia_launch_means(int ch, const Imgs &A, int n_ap, double *mu, hipStream_t st);
-void ia_launch_db_build(const LevelGeo &g, const Imgs &A, const double *mu, float4 *db, unsigned *Rbits, hipStream_t st);
+// the DB builders: ap = the A side's per-image strides (pairs) or zeros (one shared A)
+void ia_launch_means(int ch, const Imgs &A, const APairs &ap, int n_ap, double *mu, hipStream_t st);
+void ia_launch_db_build(const LevelGeo &g, const Imgs &A, const APairs &ap, const double *mu, float4 *db, unsigned *Rbits,
+                        hipStream_t st);
 void ia_launch_gather(const LevelGeo &g, const StepDesc &sd, const Imgs &B, const JobSet &jobs, const double *mu, double *q64,
                       double *qn2, float *qf, hipStream_t st);
 int ia_k3_qtmax(int KH);
@@ -25,7 +27,7 @@ void ia_launch_merge_gather(const LevelGeo &g, const StepDesc &sd, const Imgs &A
                             const Imgs &B, const NextStep &nx, bool pruned, hipStream_t st);
 void ia_launch_finish(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const double *db64, const double *q64,
                       const Winner *allwin, int world, int Mstride, const JobSet &jobs, hipStream_t st);
-void ia_launch_db64_build(const LevelGeo &g, const Imgs &A, double *db64, hipStream_t st);
+void ia_launch_db64_build(const LevelGeo &g, const Imgs &A, const APairs &ap, double *db64, hipStream_t st);
 int ia_db64_stride(int ch);
 void ia_launch_reduce_stats(const unsigned *pstat, int64_t n, unsigned long long *counters, hipStream_t st);
 // option "stamps": per launch (min start, max end) ticks over its stride workgroup slots

@@ -40,6 +40,7 @@ struct LevelPlan {
 struct LevelInputs {
   std::vector<JobPtrs> jp;  // per job: its B side on the device
   Imgs Aim, Bim;            // the A side; the B shape (images per job: JobPtrs)
+  APairs Apairs;            // the A side's per-image strides (the DB builders; 0: one shared A)
   JobSet jobs() const { return JobSet{jp[0], dev_jobs, (int)jp.size()}; }
   JobSet job(int j) const { return JobSet{jp[j], dev_jobs + j, 1}; }
   const JobPtrs *dev_jobs = nullptr;

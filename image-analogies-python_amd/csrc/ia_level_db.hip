@@ -8,14 +8,16 @@
 // ------------------------------------------------------------------------------------------
 // grid (IA_MEAN_CHUNKS, 4 CH): workgroup (b, part*CH + ch) sums chunk b of that image's pixels
 // (fixed-order strided loop + tree), then k_part_means_fold adds the chunks in order: the same
-// value on every run (a deterministic centring; any fixed mu keeps the results exact)
+// value on every run (a deterministic centring; any fixed mu keeps the results exact).  Pairs
+// (ap.n_a A images, contiguous like the A' images) are averaged over all of them: mu stays the
+// mean of what the DB holds, so the centred norms the certified bounds scale with stay small.
 #define IA_MEAN_CHUNKS 128
 template <int CH>
-__global__ void __launch_bounds__(IA_WG) k_part_means(Imgs A, int n_ap, double *part_sums) {
+__global__ void __launch_bounds__(IA_WG) k_part_means(Imgs A, int n_ap, int n_a, double *part_sums) {
   const int pc = blockIdx.y, part = pc / CH, ch = pc % CH, b = blockIdx.x;
   const double *base = part == 0 ? A.p0 : part == 1 ? A.p1 : part == 2 ? A.p2 : A.p3;
   int64_t npx = (part & 1) ? (int64_t)A.h * A.w : (int64_t)A.hc * A.wc;
-  if (part >= 2) npx *= n_ap;  // A' images are contiguous
+  npx *= part >= 2 ? n_ap : n_a;  // the images of a part are contiguous
   const int64_t i0 = npx * b / IA_MEAN_CHUNKS, i1 = npx * (b + 1) / IA_MEAN_CHUNKS;
   double s = 0.;
   for (int64_t i = i0 + threadIdx.x; i < i1; i += IA_WG) s += base[i * CH + ch];
@@ -29,12 +31,13 @@ __global__ void __launch_bounds__(IA_WG) k_part_means(Imgs A, int n_ap, double *
   if (threadIdx.x == 0) part_sums[pc * IA_MEAN_CHUNKS + b] = red[0];
 }
 template <int CH>
-__global__ void __launch_bounds__(IA_WG) k_part_means_fold(Imgs A, int n_ap, const double *part_sums, double *mu_part) {
+__global__ void __launch_bounds__(IA_WG) k_part_means_fold(Imgs A, int n_ap, int n_a, const double *part_sums,
+                                                            double *mu_part) {
   const int pc = threadIdx.x;
   if (pc >= 4 * CH) return;
   const int part = pc / CH;
   int64_t npx = (part & 1) ? (int64_t)A.h * A.w : (int64_t)A.hc * A.wc;
-  if (part >= 2) npx *= n_ap;
+  npx *= part >= 2 ? n_ap : n_a;
   double s = 0.;
   for (int b = 0; b < IA_MEAN_CHUNKS; b++) s += part_sums[pc * IA_MEAN_CHUNKS + b];
   mu_part[pc] = s / (double)npx;
@@ -44,7 +47,7 @@ __global__ void __launch_bounds__(IA_WG) k_part_means_fold(Imgs A, int n_ap, con
 // K1: DB tiles of this rank's shard (one thread per DB row)
 // ------------------------------------------------------------------------------------------
 template <int CH>
-__global__ void __launch_bounds__(IA_WG) k_db_build(LevelGeo g, Imgs A, const double *__restrict__ mu_part,
+__global__ void __launch_bounds__(IA_WG) k_db_build(LevelGeo g, Imgs A, APairs ap, const double *__restrict__ mu_part,
                                                      float4 *__restrict__ db, unsigned *__restrict__ Rbits) {
   using G = Geo<CH>;
   const int64_t pos = (int64_t)g.tile0 * IA_TILE + (int64_t)blockIdx.x * IA_WG + threadIdx.x;
@@ -62,6 +65,7 @@ __global__ void __launch_bounds__(IA_WG) k_db_build(LevelGeo g, Imgs A, const do
     pc = (int)(rem - (unsigned)pr * (unsigned)g.aw);
   }
   const Px P = make_px<CH>(A, pr, pc);
+  const Imgs Ai = ia_pair_imgs(A, ap, img);  // pairs: row img * h * w + ... reads A_img
   double norm = 0.;
 #pragma unroll
   for (int h = 0; h < 2; h++) {
@@ -74,7 +78,7 @@ __global__ void __launch_bounds__(IA_WG) k_db_build(LevelGeo g, Imgs A, const do
         if (f < G::D) {
           double a = 0.;
           if (real) {
-            a = featp<CH>(A, P, f, img) - mu_part[feat_part<CH>(f) * CH + feat_ch<CH>(f)];
+            a = featp<CH>(Ai, P, f, img) - mu_part[feat_part<CH>(f) * CH + feat_ch<CH>(f)];
             norm += a * a;
           }
           v[e] = (float)a;
@@ -96,7 +100,8 @@ __global__ void __launch_bounds__(IA_WG) k_db_build(LevelGeo g, Imgs A, const do
 
 // ------------------------------------------------------------------------------------------
 // K1b: the fp64 feature DB, row-major (row = img*h*w + r*w + c, stride Geo::DS doubles, the
-// tail zero), holding the exact pixel values of create_index's As rows (algorithms.py:63-67).
+// tail zero), holding the exact pixel values of create_index's As rows (algorithms.py:63-67):
+// [A 3x3 | A 5x5 | A'_img 3x3 | A'_img first 12], with A_img in place of A on a level of pairs.
 // The merge reranks candidates from it with contiguous 16-byte loads instead of re-gathering
 // four symmetric-padded images per row.
 // ------------------------------------------------------------------------------------------
@@ -105,7 +110,7 @@ __global__ void __launch_bounds__(IA_WG) k_db_build(LevelGeo g, Imgs A, const do
 // the rows are assembled in LDS (odd row stride: conflict-light) and leave as one contiguous
 // 64 * DS * 8 B block of 1 KiB global_store_dwordx4 per instruction.
 template <int CH>
-__global__ void __launch_bounds__(IA_WAVE) k_db64_build(LevelGeo g, Imgs A, double *__restrict__ db64) {
+__global__ void __launch_bounds__(IA_WAVE) k_db64_build(LevelGeo g, Imgs A, APairs ap, double *__restrict__ db64) {
   using G = Geo<CH>;
   constexpr int DS = G::DS, LS = DS + 1, H2 = DS / 2;
   __shared__ double t[IA_WAVE * LS];
@@ -118,9 +123,10 @@ __global__ void __launch_bounds__(IA_WAVE) k_db64_build(LevelGeo g, Imgs A, doub
     const unsigned rem = (unsigned)row - (unsigned)img * hw;
     const int pr = (int)(rem / (unsigned)g.aw), pc = (int)(rem - (unsigned)pr * (unsigned)g.aw);
     const Px P = make_px<CH>(A, pr, pc);
+    const Imgs Ai = ia_pair_imgs(A, ap, img);  // (a wave that straddles two images: per lane)
     double v[G::D];
 #pragma unroll
-    for (int f = 0; f < G::D; f++) v[f] = featp<CH>(A, P, f, img);  // all loads in flight together
+    for (int f = 0; f < G::D; f++) v[f] = featp<CH>(Ai, P, f, img);  // all loads in flight together
 #pragma unroll
     for (int f = 0; f < DS; f++) t[lane * LS + f] = f < G::D ? v[f] : 0.;
   }
@@ -248,26 +254,27 @@ __global__ void __launch_bounds__(IA_WG) k_db_build_h(LevelGeo g, const double *
 // ------------------------------------------------------------------------------------------
 // host-side launchers (called from ia_level_plan.cpp)
 // ------------------------------------------------------------------------------------------
-void ia_launch_means(int ch, const Imgs &A, int n_ap, double *mu, hipStream_t st) {
+void ia_launch_means(int ch, const Imgs &A, const APairs &ap, int n_ap, double *mu, hipStream_t st) {
   // partial sums live behind the 4 CH means in the same buffer (ia_level_plan.cpp sizes it)
   double *parts = mu + 16;
   with_ch(ch, [&](auto c) {
     constexpr int CH = decltype(c)::CH;
-    hipLaunchKernelGGL(k_part_means<CH>, dim3(IA_MEAN_CHUNKS, 4 * CH), dim3(IA_WG), 0, st, A, n_ap, parts);
-    hipLaunchKernelGGL(k_part_means_fold<CH>, dim3(1), dim3(IA_WG), 0, st, A, n_ap, (const double *)parts, mu);
+    hipLaunchKernelGGL(k_part_means<CH>, dim3(IA_MEAN_CHUNKS, 4 * CH), dim3(IA_WG), 0, st, A, n_ap, ap.n_a, parts);
+    hipLaunchKernelGGL(k_part_means_fold<CH>, dim3(1), dim3(IA_WG), 0, st, A, n_ap, ap.n_a, (const double *)parts, mu);
   });
 }
 
-void ia_launch_db_build(const LevelGeo &g, const Imgs &A, const double *mu, float4 *db, unsigned *Rbits, hipStream_t st) {
+void ia_launch_db_build(const LevelGeo &g, const Imgs &A, const APairs &ap, const double *mu, float4 *db, unsigned *Rbits,
+                        hipStream_t st) {
   const int64_t rows = (int64_t)(g.tile1 - g.tile0) * IA_TILE;
   with_ch(g.ch, [&](auto c) {
-    hipLaunchKernelGGL(k_db_build<decltype(c)::CH>, dim3(cdiv(rows, IA_WG)), dim3(IA_WG), 0, st, g, A, mu, db, Rbits);
+    hipLaunchKernelGGL(k_db_build<decltype(c)::CH>, dim3(cdiv(rows, IA_WG)), dim3(IA_WG), 0, st, g, A, ap, mu, db, Rbits);
   });
 }
 
-void ia_launch_db64_build(const LevelGeo &g, const Imgs &A, double *db64, hipStream_t st) {
+void ia_launch_db64_build(const LevelGeo &g, const Imgs &A, const APairs &ap, double *db64, hipStream_t st) {
   with_ch(g.ch, [&](auto c) {
-    hipLaunchKernelGGL(k_db64_build<decltype(c)::CH>, dim3(cdiv(g.NA, IA_WAVE)), dim3(IA_WAVE), 0, st, g, A, db64);
+    hipLaunchKernelGGL(k_db64_build<decltype(c)::CH>, dim3(cdiv(g.NA, IA_WAVE)), dim3(IA_WAVE), 0, st, g, A, ap, db64);
   });
 }
 int ia_db64_stride(int ch) { return ch == 1 ? Geo<1>::DS : ch == 2 ? Geo<2>::DS : Geo<3>::DS; }

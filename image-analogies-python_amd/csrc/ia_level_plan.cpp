@@ -134,6 +134,8 @@ int check_level_args(const ia_level_args *a) {
   if (a->mem != IA_MEM_HOST && a->mem != IA_MEM_DEVICE) return fail(IA_EINVAL, "ia_synthesize_level: bad mem kind");
   if ((a->dbg_src == nullptr) != (a->dbg_dist == nullptr))
     return fail(IA_EINVAL, "ia_synthesize_level: dbg_src and dbg_dist are given together or not at all");
+  if (a->n_a != 0 && a->n_a != 1 && a->n_a != a->n_ap)
+    return fail(IA_EINVAL, "ia_synthesize_level: n_a must be 0 or 1 (one A shared by every A') or n_ap (one A per A')");
   if ((int64_t)a->n_ap * a->a_h * a->a_w >= (int64_t)INT32_MAX)
     return fail(IA_EINVAL, "ia_synthesize_level: DB rows exceed int32 row ids");
   return IA_OK;
@@ -150,6 +152,7 @@ int plan_shards(ia_ctx *c, const ia_level_args *args, int J, LevelPlan &P) {
   P.J = J;
   P.DP = 2 * g.KH;
   g.n_ap = a->n_ap;
+  g.n_a = a->n_a > 1 ? a->n_a : 1;
   g.ah = a->a_h;
   g.aw = a->a_w;
   g.ahc = (a->a_h + 1) / 2;
@@ -303,12 +306,13 @@ int stage_level(ia_ctx *c, const ia_level_args *args, const LevelPlan &P, LevelI
   const int64_t NB = P.NB;
   int rc;
   const void *dA, *dAc, *dAp, *dApc;
-  if ((rc = stage(c, c->A, a->A, nA * 8, a->mem, &dA)) || (rc = stage(c, c->Ac, a->Ac, nAc * 8, a->mem, &dAc)) ||
+  if ((rc = stage(c, c->A, a->A, nA * g.n_a * 8, a->mem, &dA)) || (rc = stage(c, c->Ac, a->Ac, nAc * g.n_a * 8, a->mem, &dAc)) ||
       (rc = stage(c, c->Ap, a->Ap, nA * g.n_ap * 8, a->mem, &dAp)) ||
       (rc = stage(c, c->Apc, a->Apc, nAc * g.n_ap * 8, a->mem, &dApc)))
     return rc;
   in.Aim = Imgs{(const double *)dAc, (const double *)dA, (const double *)dApc, (const double *)dAp,
                 g.ah, g.aw, g.ahc, g.awc, (int64_t)nA, (int64_t)nAc};
+  in.Apairs = g.n_a > 1 ? APairs{(int64_t)nA, (int64_t)nAc, g.n_a} : APairs{0, 0, 1};
   in.Bim = Imgs{nullptr, nullptr, nullptr, nullptr, g.bh, g.bw, g.bhc, g.bwc, 0, 0};
   if ((int)c->jb.size() < J) c->jb.resize(J);
   in.jp.resize(J);
@@ -366,7 +370,7 @@ int probe_matcher(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, bool *us
   for (int j = 0; j < P.J; j++) {
     const JobPtrs &p = in.jp[j];
     const double *arrs[8] = {j ? nullptr : A.p1, j ? nullptr : A.p0, j ? nullptr : A.p3, j ? nullptr : A.p2, p.B, p.Bc, p.Bpc, p.Bp};
-    const int64_t ns8[8] = {(int64_t)P.nA, (int64_t)P.nAc, (int64_t)(P.nA * g.n_ap), (int64_t)(P.nAc * g.n_ap),
+    const int64_t ns8[8] = {(int64_t)(P.nA * g.n_a), (int64_t)(P.nAc * g.n_a), (int64_t)(P.nA * g.n_ap), (int64_t)(P.nAc * g.n_ap),
                             (int64_t)P.nB, (int64_t)P.nBc, (int64_t)P.nBc, (int64_t)P.nB};
     ia_launch_absmax(arrs, ns8, c->absmax.as<unsigned>(), c->st);
   }
@@ -402,16 +406,16 @@ int build_level_db(ia_ctx *c, LevelPlan &P, const LevelInputs &in, double *ufac)
   LevelGeo &g = P.g;
   int rc;
   HIP_TRY(hipEventRecord(c->lv0, c->st));
-  ia_launch_means(g.ch, in.Aim, g.n_ap, c->mu.as<double>(), c->st);
+  ia_launch_means(g.ch, in.Aim, in.Apairs, g.n_ap, c->mu.as<double>(), c->st);
   HIP_TRY(hipEventRecord(c->kb[0], c->st));
-  ia_launch_db64_build(g, in.Aim, c->db64.as<double>(), c->st);
+  ia_launch_db64_build(g, in.Aim, in.Apairs, c->db64.as<double>(), c->st);
   HIP_TRY(hipEventRecord(c->kb[1], c->st));
   *ufac = 0.;
   if (P.prune && (rc = prepare_prune(c, g, c->mu.as<double>(), P.Wsh, ufac))) return rc;
   HIP_TRY(hipEventRecord(c->kb[2], c->st));
   if (P.ns > 0) {
     if (P.use_h) ia_launch_db_build_h(g, in.Aim, c->db64.as<double>(), c->mu.as<double>(), c->db.p, c->Rbits.as<unsigned>(), c->st);
-    else ia_launch_db_build(g, in.Aim, c->mu.as<double>(), c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
+    else ia_launch_db_build(g, in.Aim, in.Apairs, c->mu.as<double>(), c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
   }
   HIP_TRY(hipEventRecord(c->kb[3], c->st));
   HIP_TRY(hipEventRecord(c->lv1, c->st));

@@ -746,9 +746,9 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
   for (int j = 0; j < n_jobs; j++) {
     const ia_level_args *x = &args[j];
     if ((rc = check_level_args(x))) return rc;
-    if (x->ch != a->ch || x->n_ap != a->n_ap || x->a_h != a->a_h || x->a_w != a->a_w || x->b_h != a->b_h ||
+    if (x->ch != a->ch || x->n_ap != a->n_ap || x->n_a != a->n_a || x->a_h != a->a_h || x->a_w != a->a_w || x->b_h != a->b_h ||
         x->b_w != a->b_w || x->mem != a->mem)
-      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch has the same shapes, channels and mem kind");
+      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch has the same shapes, channels, n_a and mem kind");
     if (x->A != a->A || x->Ac != a->Ac || x->Ap != a->Ap || x->Apc != a->Apc)
       return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch shares the A side (same A / A' buffers)");
   }

@@ -130,7 +130,7 @@ int accumulate_stats(ia_ctx *c, const LevelPlan &P, const StampSlots &stamps, co
     }
     const int DSb = ia_db64_stride(g.ch);
     stats->k1b_ms += ms_k1b;
-    stats->k1b_bytes += (double)(P.nA + P.nAc) * (1 + g.n_ap) * 8 + (double)g.NA * DSb * 8;
+    stats->k1b_bytes += (double)(P.nA + P.nAc) * (g.n_a + g.n_ap) * 8 + (double)g.NA * DSb * 8;
     if (P.ns > 0 && P.use_h) {
       stats->k1_ms += ms_k1;
       stats->k1_bytes += (double)std::min<int64_t>((int64_t)P.ns * IA_TILE, g.NA) * DSb * 8 + (double)P.ns * P.tile_bytes;

@@ -18,7 +18,7 @@ import warnings
 import numpy as np
 
 from . import _native
-from .algorithms import default_context
+from .algorithms import a_levels, default_context
 from .config import save_metadata, setup_vars
 from .img_preprocess import (compress_values, compute_gaussian_pyramid, convert_to_RGB, convert_to_YIQ,
                              initialize_Bp, remap_luminance)
@@ -37,37 +37,54 @@ def _imsave(path, img):
 
 
 def img_setup(A_fname, Ap_fname_list, B_fname, out_path, c):
-    """image_analogies.py:17-94.  File names may also be numpy arrays."""
+    """image_analogies.py:17-94.  File names may also be numpy arrays.
+    A_fname may be a list or tuple with one entry per Ap_fname_list entry: training pairs
+    (A_i, A'_i), every image of one shape.  Each A_i is then scaled, converted, compressed and
+    reduced on its own, remap_lum remaps each pair (A_i, A'_i) with A_i's own mean and deviation,
+    and the first return value is the list of the A_i's pyramids."""
     check_windows(c)
     os.makedirs(out_path, exist_ok=True)
-    A_orig, B_orig = _imread(A_fname), _imread(B_fname)
+    pairs = isinstance(A_fname, (list, tuple))
+    if pairs and len(A_fname) != len(Ap_fname_list):
+        raise ValueError("a list of A images needs one entry per A' image (got %d for %d)"
+                         % (len(A_fname), len(Ap_fname_list)))
+    A_orig_list = [_imread(f) for f in (A_fname if pairs else [A_fname])]
+    A_orig, B_orig = A_orig_list[0], _imread(B_fname)
     if A_orig.ndim != B_orig.ndim:
         raise ValueError('A and B must have the same number of channels')
+    if any(x.shape != A_orig.shape for x in A_orig_list):
+        raise ValueError('every A of a pair list must have one shape (pairs of different sizes are not supported)')
     Ap_orig_list = [_imread(f) for f in Ap_fname_list]
     for Ap_orig in Ap_orig_list:
         if Ap_orig.shape != A_orig.shape:
             raise ValueError("every A' must be aligned with A (same shape)")
     # 0..255 vs 0..1 detection; the reference tests the FIRST ROW of the LAST A' (quirk, :33)
     scale = lambda x: 255. if np.max(x) > 1.0 else 1.0
-    sA, sB, sAp = scale(A_orig), scale(B_orig), scale(Ap_orig_list[-1][0])
+    sB, sAp = scale(B_orig), scale(Ap_orig_list[-1][0])
 
     gpu = default_context() if getattr(c, 'gpu_preprocess', True) else None   # SURVEY §8 F4
     if c.convert:
-        A = convert_to_YIQ(A_orig / sA, gpu)[:, :, 0]
+        A_list = [convert_to_YIQ(x / scale(x), gpu)[:, :, 0] for x in A_orig_list]
         B_yiq = convert_to_YIQ(B_orig / sB, gpu)
         B = B_yiq[:, :, 0]
         Ap_list = [convert_to_YIQ(x / sAp, gpu)[:, :, 0] for x in Ap_orig_list]
     else:
-        A, B = A_orig / sA, B_orig / sB
+        A_list, B = [x / scale(x) for x in A_orig_list], B_orig / sB
         Ap_list = [x / sAp for x in Ap_orig_list]
     if c.remap_lum:
-        A, Ap_list = remap_luminance(A, Ap_list, B)
+        if pairs:
+            remapped = [remap_luminance(a, [ap], B) for a, ap in zip(A_list, Ap_list)]
+            A_list, Ap_list = [r[0] for r in remapped], [r[1][0] for r in remapped]
+        else:
+            A_list[0], Ap_list = remap_luminance(A_list[0], Ap_list, B)
     if not c.init_rand:
         B_orig_pyr = compute_gaussian_pyramid(B, c.n_sm, c.n_levels, gpu)
-    A, B = compress_values(A, B, c.AB_weight)
-    c.num_ch, c.padding_sm, c.padding_lg, c.weights = setup_vars(A)
+    compressed = [compress_values(a, B, c.AB_weight) for a in A_list]   # (ratio A_i, ratio B) each
+    A_list, B = [x[0] for x in compressed], compressed[0][1]
+    c.num_ch, c.padding_sm, c.padding_lg, c.weights = setup_vars(A_list[0])
 
-    A_pyr = compute_gaussian_pyramid(A, c.n_sm, c.n_levels, gpu)
+    A_pyr_list = [compute_gaussian_pyramid(a, c.n_sm, c.n_levels, gpu) for a in A_list]
+    A_pyr = A_pyr_list[0]
     B_pyr = compute_gaussian_pyramid(B, c.n_sm, c.n_levels, gpu)
     Ap_pyr_list = [compute_gaussian_pyramid(x, c.n_sm, c.n_levels, gpu) for x in Ap_list]
     if c.convert:
@@ -90,7 +107,7 @@ def img_setup(A_fname, Ap_fname_list, B_fname, out_path, c):
         c.max_levels = len(B_pyr)
     src = B_pyr if c.init_rand else B_orig_pyr
     Bp_pyr = initialize_Bp(src, init_rand=c.init_rand, seed=getattr(c, 'seed', None))
-    return A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, color_pyr_list, c
+    return (A_pyr_list if pairs else A_pyr), Ap_pyr_list, B_pyr, Bp_pyr, color_pyr_list, c
 
 
 def check_windows(c):
@@ -107,6 +124,7 @@ def synthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, c, ctx=None, stats=Non
     Bp_pyr levels 1..max_levels-1 are synthesised in place; returns ({level: s}, {level: im}).
     debug: a dict that receives {level: {'src', 'dist'}} per-pixel debug records
     (_native.Context.synthesize_level).
+    A_pyr: one pyramid, or a list of pyramids with one per A' (algorithms.is_pyramid_list).
     Warns when a kappa decision sat where libm's pow (the reference's `** 2`) could round the
     other way than the kernel's y * y (ia_stats.kappa_ambiguous; 0 on every fixture)."""
     check_windows(c)
@@ -120,7 +138,8 @@ def synthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, c, ctx=None, stats=Non
         kf = 1 + (2 ** (level - L)) * c.k          # image_analogies.py:206
         dbg = None if debug is None else debug.setdefault(level, {})
         S[level], IM[level] = ctx.synthesize_level(
-            A_pyr[level], A_pyr[level - 1], [p[level] for p in Ap_pyr_list], [p[level - 1] for p in Ap_pyr_list],
+            a_levels(A_pyr, level), a_levels(A_pyr, level - 1), [p[level] for p in Ap_pyr_list],
+            [p[level - 1] for p in Ap_pyr_list],
             B_pyr[level], B_pyr[level - 1], Bp_pyr[level - 1], Bp_pyr[level], c.weights, kf, stats, debug=dbg)
         if on_level is not None:
             on_level(level, S, IM)
@@ -210,7 +229,8 @@ def image_analogies_main(A_fname, Ap_fname_list, B_fname, out_path, c, debug=Fal
     begin = time.time()
     A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, color_pyr_list, c = img_setup(A_fname, Ap_fname_list, B_fname, out_path, c)
     names = ['A_fname', 'Ap_fname_list', 'B_fname', 'c.convert', 'c.remap_lum', 'c.init_rand', 'c.AB_weight', 'c.k']
-    vals = [A_fname if isinstance(A_fname, str) else '<array>',
+    name = lambda f: f if isinstance(f, str) else '<array>'
+    vals = [[name(f) for f in A_fname] if isinstance(A_fname, (list, tuple)) else name(A_fname),
             [f if isinstance(f, str) else '<array>' for f in Ap_fname_list],
             B_fname if isinstance(B_fname, str) else '<array>', c.convert, c.remap_lum, c.init_rand, c.AB_weight, c.k]
     save_metadata(out_path, names, vals)

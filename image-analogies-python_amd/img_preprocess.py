@@ -42,6 +42,40 @@ def remap_luminance(A, Ap_list, B):
     return gain * (A - mA) + mB, [gain * (Ap - mA) + mB for Ap in Ap_list]
 
 
+# the eight symmetries of a rectangle's pixel grid; the last four swap the axes
+_TRANSFORMS = {
+    'lr': lambda x: x[:, ::-1],
+    'ud': lambda x: x[::-1],
+    'rot180': lambda x: x[::-1, ::-1],
+    'rot90': lambda x: np.swapaxes(x, 0, 1)[::-1],
+    'rot270': lambda x: np.swapaxes(x, 0, 1)[:, ::-1],
+    'transpose': lambda x: np.swapaxes(x, 0, 1),
+    'transverse': lambda x: np.swapaxes(x, 0, 1)[::-1, ::-1],
+}
+_TRANSPOSING = ('rot90', 'rot270', 'transpose', 'transverse')
+
+
+def augment_pairs(A, Ap, transforms=('lr', 'ud', 'rot180')):
+    """Training pairs from one: ([A, t1(A), ...], [A', t1(A'), ...]), the original pair first, then
+    one pair per entry of `transforms` ('lr', 'ud', 'rot180', and for square images 'rot90',
+    'rot270', 'transpose', 'transverse'), A and A' under the same transform.  Every pair keeps
+    the shape of the original (the pairs of one job are of equal shape), which is why the four
+    axis-swapping transforms take square images only.  Pass the two lists as A_fname and
+    Ap_fname_list of image_analogies_main."""
+    A, Ap = np.asarray(A), np.asarray(Ap)
+    if A.shape != Ap.shape or A.ndim not in (2, 3):
+        raise ValueError("augment_pairs: A and A' must be images of one shape (got %s and %s)" % (A.shape, Ap.shape))
+    As, Aps = [A], [Ap]
+    for t in transforms:
+        if t not in _TRANSFORMS:
+            raise ValueError('augment_pairs: unknown transform %r (one of %s)' % (t, sorted(_TRANSFORMS)))
+        if t in _TRANSPOSING and A.shape[0] != A.shape[1]:
+            raise ValueError('augment_pairs: %r swaps the axes and needs a square image (got %s)' % (t, A.shape[:2]))
+        As.append(np.ascontiguousarray(_TRANSFORMS[t](A)))
+        Aps.append(np.ascontiguousarray(_TRANSFORMS[t](Ap)))
+    return As, Aps
+
+
 def compress_values(A, B, ratio):
     """img_preprocess.py:43-44."""
     return ratio * A, ratio * B

@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _native
 from . import config as _config
+from .algorithms import a_levels
 from .img_preprocess import compute_gaussian_pyramid, initialize_Bp
 
 
@@ -44,6 +45,8 @@ def cfg5_jobs(kappas=(0.5, 1, 2, 5, 10, 15, 20, 25), depths=range(2, 10), seed=3
 
 class Sweep(object):
     """Host side of a sweep: the full pyramids of A, A'_i, B and each job's B' pyramid.
+    A: one image, or a list / tuple with one image per A' (pairs (A_i, A'_i) of equal shape); A_pyr
+    is then a list of pyramids (algorithms.is_pyramid_list).
     full_levels(j) maps job j's level l to the full pyramid's index f = l + (Lf - L_j)."""
 
     def __init__(self, A, Ap_list, B, jobs, weights=None, min_size=None, level_align='coarse'):
@@ -54,7 +57,13 @@ class Sweep(object):
         min_size = _config.n_sm if min_size is None else min_size
         if level_align not in ('coarse', 'fine'):
             raise ValueError("level_align must be 'coarse' or 'fine'")
-        self.A_pyr = compute_gaussian_pyramid(A, min_size)
+        self.pairs = isinstance(A, (list, tuple))
+        A_list = list(A) if self.pairs else [A]
+        A = A_list[0]
+        if self.pairs and (len(A_list) != len(Ap_list) or any(np.shape(x) != np.shape(A) for x in A_list)):
+            raise ValueError("a list of A images needs one image per A', all of one shape")
+        A_pyrs = [compute_gaussian_pyramid(x, min_size) for x in A_list]
+        self.A_pyr = A_pyrs[0]
         self.Ap_pyr_list = [compute_gaussian_pyramid(Ap, min_size) for Ap in Ap_list]
         self.B_pyr = compute_gaussian_pyramid(B, min_size)
         Lf = min(len(self.A_pyr), len(self.B_pyr))
@@ -65,8 +74,10 @@ class Sweep(object):
         self.Ap_pyr_list = [p[sl] for p in self.Ap_pyr_list]
         for a, b in zip(self.A_pyr, self.B_pyr):   # paired levels: same depth below the coarsest
             assert a.ndim == b.ndim, 'A and B differ in channels'
+        if self.pairs:
+            self.A_pyr = [p[sl] for p in A_pyrs]
         self.Lf = Lf
-        ch = 1 if A.ndim == 2 else A.shape[2]
+        ch = 1 if np.ndim(A) == 2 else np.shape(A)[2]
         self.weights = (_config.compute_weights(_config.n_sm, _config.n_lg, _config.n_half, ch)
                         if weights is None else weights)
         self.jobs = list(jobs)
@@ -106,7 +117,7 @@ class Sweep(object):
         IM = {j: {} for j in jobs}
         stats = stats if stats is not None else _native.Stats()
         for f, part in self.schedule(jobs, max_batch if batched else 1):
-            A, Ac = self.A_pyr[f], self.A_pyr[f - 1]
+            A, Ac = a_levels(self.A_pyr, f), a_levels(self.A_pyr, f - 1)
             Ap = [p[f] for p in self.Ap_pyr_list]
             Apc = [p[f - 1] for p in self.Ap_pyr_list]
             specs = [dict(B=self.B_pyr[f], Bc=self.B_pyr[f - 1], Bpc=Bp[j][l - 1], Bp=Bp[j][l], weights=self.weights,
@@ -125,7 +136,9 @@ class DeviceSweep(object):
     def __init__(self, sweep, jobs, torch, dev):
         t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
         self.sw, self.jobs, self.torch = sweep, list(jobs), torch
-        self.A = [t(x) for x in sweep.A_pyr]
+        self.n_a = len(sweep.A_pyr) if sweep.pairs else 0   # pairs: A stacked like A'
+        self.A = ([t(np.stack([p[f] for p in sweep.A_pyr])) for f in range(sweep.Lf)] if sweep.pairs
+                  else [t(x) for x in sweep.A_pyr])
         self.Ap = [t(np.stack([p[f] for p in sweep.Ap_pyr_list])) for f in range(sweep.Lf)]
         self.B = [t(x) for x in sweep.B_pyr]
         self.W = t(sweep.weights)
@@ -134,7 +147,7 @@ class DeviceSweep(object):
         hw = lambda x: int(np.prod(x.shape[:2]))
         self.S = {j: [torch.empty((hw(x), 2), dtype=torch.int32, device=dev) for x in self.Bp0[j]] for j in self.jobs}
         self.IM = {j: [torch.empty(hw(x), dtype=torch.int32, device=dev) for x in self.Bp0[j]] for j in self.jobs}
-        self.ch = 1 if sweep.A_pyr[0].ndim == 2 else sweep.A_pyr[0].shape[2]
+        self.ch = 1 if sweep.B_pyr[0].ndim == 2 else sweep.B_pyr[0].shape[2]
 
     def run(self, ctx, stats, batched=True, max_batch=16):
         """ctx: one libia Context, or a list of them: the jobs are then dealt round-robin over the
@@ -177,5 +190,5 @@ class DeviceSweep(object):
                          Bpc=self.Bp[j][l - 1].data_ptr(), Bp=self.Bp[j][l].data_ptr(), weights=self.W.data_ptr(),
                          s_out=self.S[j][l].data_ptr(), im_out=self.IM[j][l].data_ptr()) for j, l in part]
             kfs = [sw.kappa_factor(j, l) for j, l in part]
-            ctx.synthesize_levels_device(self.ch, len(sw.Ap_pyr_list), self.A[f].shape[:2], self.B[f].shape[:2], ptrs,
-                                         kfs, stats)
+            ctx.synthesize_levels_device(self.ch, len(sw.Ap_pyr_list), sw.Ap_pyr_list[0][f].shape[:2],
+                                         self.B[f].shape[:2], ptrs, kfs, stats, n_a=self.n_a)

@@ -11,6 +11,7 @@ import numpy as np
 from scipy.ndimage import gaussian_filter
 
 from . import config as _config
+from .algorithms import a_levels, is_pyramid_list
 from .img_preprocess import compute_gaussian_pyramid, initialize_Bp
 
 
@@ -31,13 +32,22 @@ def filt(A):
 
 class Job(object):
     """Pyramids + parameters of one synthesis job (everything image_analogies_main derives
-    before its level loop, image_analogies.py:103-123), aligned coarsest-first."""
+    before its level loop, image_analogies.py:103-123), aligned coarsest-first.  A_pyr is one
+    pyramid, or a list of pyramids with one per A' (pairs (A_i, A'_i), algorithms.is_pyramid_list)."""
 
     def __init__(self, A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, k, weights):
         self.A_pyr, self.Ap_pyr_list, self.B_pyr, self.Bp_init = A_pyr, Ap_pyr_list, B_pyr, Bp_pyr
         self.k = k
         self.weights = weights
-        self.L = min(len(A_pyr), len(B_pyr))
+        self.pairs = is_pyramid_list(A_pyr)
+        if self.pairs and len(A_pyr) != len(Ap_pyr_list):
+            raise ValueError("a list of A pyramids needs one per A' pyramid")
+        self.A0_pyr = A_pyr[0] if self.pairs else A_pyr   # shapes and depth: the pairs are of one shape
+        self.L = min(len(self.A0_pyr), len(B_pyr))
+
+    def A_levels(self, level):
+        """level `level` of the A side as Context.synthesize_level takes it (an array, or one per pair)"""
+        return a_levels(self.A_pyr, level)
 
     def kappa_factor(self, level):
         return 1 + (2 ** (level - self.L)) * self.k   # image_analogies.py:206
@@ -49,10 +59,10 @@ class Job(object):
 
     def flops(self):
         """Algorithmic NN flops of one run: sum_l 2 * D * N_A,l * N_B,l."""
-        ch = 1 if self.A_pyr[0].ndim == 2 else self.A_pyr[0].shape[2]
+        ch = 1 if self.A0_pyr[0].ndim == 2 else self.A0_pyr[0].shape[2]
         D = 55 * ch
         nap = len(self.Ap_pyr_list)
-        return float(sum(2.0 * D * nap * np.prod(self.A_pyr[l].shape[:2]) * np.prod(self.B_pyr[l].shape[:2])
+        return float(sum(2.0 * D * nap * np.prod(self.A0_pyr[l].shape[:2]) * np.prod(self.B_pyr[l].shape[:2])
                          for l in range(1, self.L)))
 
 

@@ -117,6 +117,10 @@ typedef struct {
 
 /* One pyramid level (image_analogies.py:130-239).  Shapes: A/A' level l is (a_h, a_w[, ch]),
  * level l-1 is (ceil(a_h/2), ceil(a_w/2)[, ch]); same for B.  Ap / Apc stack n_ap images.
+ * The A side is one image shared by every A' (the reference, algorithms.py:63-67: n_a = 0 or 1)
+ * or one image per A' (n_a = n_ap: training pairs (A_i, A'_i) of equal shape, A / Ac stacked the
+ * way Ap / Apc are).  DB row img * a_h * a_w + r * a_w + c holds the features of pixel (r, c) of
+ * pair img: [A_i 3x3 | A_i 5x5 | A'_i 3x3 | A'_i first 12] with A_i = A for a shared A.
  * Bp: in = initial B' level (initialize_Bp, img_preprocess.py:66-78), out = synthesised.
  * s_out (N x 2, row/col in A) and im_out (N) are the reference's s / im lists for this level. */
 typedef struct {
@@ -147,13 +151,17 @@ typedef struct {
  *          which is not always v's correctly rounded square root squared: the host applies it. */
   int32_t *dbg_src;
   double *dbg_dist;
+  int n_a;         /* A images: 0 or 1 = one A shared by all n_ap A' images; n_ap = one A per A'
+                    * (A and Ac stack n_a images).  Any other value is IA_EINVAL.  Last field, so
+                    * callers built against version 1 (which zero-initialise the struct) keep
+                    * their layout and their meaning */
 } ia_level_args;
 
 /* ---- context ---------------------------------------------------------------------------- */
 int ia_init(int device, ia_ctx **out);
 void ia_destroy(ia_ctx *ctx);
 const char *ia_last_error(void);
-int ia_version(void);
+int ia_version(void);  /* 2: ia_level_args.n_a (1: the struct ended at dbg_dist) */
 /* Options: "time_dist" = S (0 = off): bracket the MFMA distance launches of every S-th
  * wavefront step with HIP events; ia_stats.dist_ms / dist_flops_timed then give the kernel's
  * measured device time and algorithmic flops (bench.py roofline).
@@ -273,8 +281,8 @@ int ia_xchg_open(ia_ctx *ctx, int rank, int world, const unsigned char *handles)
 int ia_synthesize_level(ia_ctx *ctx, const ia_level_args *args, ia_stats *stats);
 /* The same level for n_jobs independent jobs at once (multi_script.py's parameter sweeps,
  * multi_script.py:13-32: kappa / pyramid depth change, the A side does not).  args[0..n_jobs)
- * must share the A side (identical A, Ac, Ap, Apc pointers: one feature DB is built) and every
- * shape, channel count and mem kind; B, Bc, Bpc, Bp, weights, kappa_factor, outputs and debug
+ * must share the A side (identical A, Ac, Ap, Apc pointers and n_a: one feature DB is built) and
+ * every shape, channel count and mem kind; B, Bc, Bpc, Bp, weights, kappa_factor, outputs and debug
  * buffers are per job.  Every wavefront step gathers the queries of all jobs and runs ONE
  * distance scan over the DB for them (the DB is streamed once per step, not once per job), then
  * each job's coherence / kappa / writeback.  Results are those of n_jobs separate
