@@ -12,3 +12,4 @@ root, which maps this hyphenated directory to that package name).
 __version__ = '0.1.0'
 
 from .img_preprocess import augment_pairs  # noqa: E402,F401  (ia_amd.augment_pairs)
+from .algorithms import build_similarity   # noqa: E402,F401  (ia_amd.build_similarity)

@@ -60,7 +60,8 @@ class Stats(ctypes.Structure):
                 ('stamp_gaps', ctypes.c_int64), ('stamp_window_ms', ctypes.c_double), ('prune_rows', ctypes.c_int64),
                 ('k3p_stamp_start_ms', ctypes.c_double), ('k3p_stamp_wg_ms', ctypes.c_double),
                 ('stamp_gap_sm_ms', ctypes.c_double), ('stamp_gaps_sm', ctypes.c_int64),
-                ('k3p_bytes_unique_all', ctypes.c_double)]
+                ('k3p_bytes_unique_all', ctypes.c_double),
+                ('kcoh_levels', ctypes.c_int64), ('kcoh_fallbacks', ctypes.c_int64), ('kcoh_candidates', ctypes.c_int64)]
 
     # fields that describe only the levels with the largest DB seen (build_rows / prune_rows)
     _BUILD = ('k1b_ms', 'k1b_bytes', 'k1_ms', 'k1_bytes', 'build_levels')
@@ -97,6 +98,8 @@ EXPORTS = {
     'ia_comm_init': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]),
     'ia_xchg_alloc': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p]),
     'ia_xchg_open': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]),
+    'ia_synthesize_levels_kcoh': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LevelArgs), ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_int, ctypes.POINTER(Stats)]),
     'ia_pipeline_depend': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     'ia_pipeline_generation': (ctypes.c_int, [ctypes.c_void_p]),
     'ia_synthesize_level': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LevelArgs), ctypes.POINTER(Stats)]),
@@ -109,6 +112,7 @@ EXPORTS = {
     'ia_index_query_knn': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_void_p]),
     'ia_index_knn_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'ia_index_similarity': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     'ia_index_count_radius': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                              ctypes.c_void_p]),
     'ia_index_query_radius': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -327,7 +331,7 @@ class Context(object):
         return lib().ia_pipeline_generation(self._h)
 
     def synthesize_level(self, A, Ac, Ap_list, Apc_list, B, Bc, Bpc, Bp, weights, kappa_factor, stats=None,
-                         debug=None):
+                         debug=None, sim=None):
         """ia_synthesize_level on host numpy arrays.  A / Ac: one array each (the A every A' shares)
         or lists with one array per A' (pairs (A_i, A'_i) of equal shape; IAShapeError, a
         ValueError, otherwise).  Bp (fp64, C-contiguous) is updated in place
@@ -335,17 +339,21 @@ class Context(object):
         s (N, 2) int32 source pixel in A', im (N,) int32 source A' image, raster order.
         debug: a dict to receive the debug=True per-pixel records (include/ia.h dbg_src/dbg_dist):
         'src' (N, 6) int32 [p_app row, col, img, r_star row, col, has_coh], 'dist' (N, 2) fp64
-        [d_app, d_coh] (image_analogies.py:224-240), finished on the host as numpy does."""
+        [d_app, d_coh] (image_analogies.py:224-240), finished on the host as numpy does.
+        sim: (N_A, K) similarity sets of the level's DB rows (ExactIndex.similarity): the level runs
+        by k-coherence search (include/ia.h ia_synthesize_levels_kcoh) - not the reference's result unless
+        K = N_A - 1; None: the exact path."""
         job = dict(B=B, Bc=Bc, Bpc=Bpc, Bp=Bp, weights=weights, kappa_factor=kappa_factor, debug=debug)
-        return self.synthesize_levels(A, Ac, Ap_list, Apc_list, [job], stats)[0]
+        return self.synthesize_levels(A, Ac, Ap_list, Apc_list, [job], stats, sim=sim)[0]
 
-    def synthesize_levels(self, A, Ac, Ap_list, Apc_list, jobs, stats=None):
+    def synthesize_levels(self, A, Ac, Ap_list, Apc_list, jobs, stats=None, sim=None):
         """ia_synthesize_levels: one level of several jobs that share the A side (A, A' levels l and
         l-1), e.g. a kappa / pyramid-depth sweep (multi_script.py).  jobs: list of dicts with
         B, Bc, Bpc, Bp (updated in place), weights, kappa_factor and optionally debug (a dict, see
         synthesize_level).  A / Ac may be lists, one image per A' (pairs), as in synthesize_level.
         One DB, one distance scan per wavefront step for all jobs.  Returns
-        [(s, im)] per job, each identical to a separate synthesize_level call."""
+        [(s, im)] per job, each identical to a separate synthesize_level call.
+        sim: the A side's similarity sets, shared by every job (synthesize_level)."""
         if not 1 <= len(jobs) <= 32:
             raise IAError('synthesize_levels: 1..32 jobs per call (got %d)' % len(jobs))
         Ap = _c64(np.stack(Ap_list))
@@ -357,6 +365,12 @@ class Context(object):
         else:
             A, Ac = _c64(A), _c64(Ac)
             A_all, Ac_all = A, Ac
+        sim_k = 0
+        if sim is not None:
+            sim = np.ascontiguousarray(sim, dtype=np.int32)
+            if sim.ndim != 2 or sim.shape[0] != Ap.shape[0] * A.shape[0] * A.shape[1]:
+                raise IAError('sim must be (N_A, K) = (%d, K) (got %s)' % (Ap.shape[0] * A.shape[0] * A.shape[1], sim.shape))
+            sim_k = sim.shape[1]
         keep, args, outs = [], [], []
         for jb in jobs:
             B, Bc, Bpc, Bp, w = _c64(jb['B']), _c64(jb['Bc']), _c64(jb['Bpc']), jb['Bp'], _c64(jb['weights'])
@@ -378,7 +392,11 @@ class Context(object):
             outs.append((s, im, dsrc, ddist, jb.get('debug')))
         arr = (LevelArgs * len(args))(*args)
         st = stats if stats is not None else Stats()
-        check(lib().ia_synthesize_levels(self._h, arr, len(args), ctypes.byref(st)), 'ia_synthesize_levels')
+        if sim is None:
+            check(lib().ia_synthesize_levels(self._h, arr, len(args), ctypes.byref(st)), 'ia_synthesize_levels')
+        else:
+            check(lib().ia_synthesize_levels_kcoh(self._h, arr, len(args), _ptr(sim), sim_k, ctypes.byref(st)),
+                  'ia_synthesize_levels_kcoh')
         res = []
         for s, im, dsrc, ddist, debug in outs:
             if debug is not None:
@@ -391,16 +409,19 @@ class Context(object):
             res.append((s, im))
         return res
 
-    def synthesize_level_device(self, ch, n_ap, a_hw, b_hw, ptrs, kappa_factor, stats=None, n_a=0):
+    def synthesize_level_device(self, ch, n_ap, a_hw, b_hw, ptrs, kappa_factor, stats=None, n_a=0, sim=None, sim_k=0):
         """Same on device pointers (IA_MEM_DEVICE): ptrs = dict of int addresses for
         A, Ac, Ap, Apc, B, Bc, Bpc, Bp, weights, s_out, im_out (e.g. torch tensor data_ptr()).
-        n_a = n_ap: A and Ac stack one image per A' (pairs); 0 or 1: one shared A."""
-        return self.synthesize_levels_device(ch, n_ap, a_hw, b_hw, [ptrs], [kappa_factor], stats, n_a=n_a)
+        n_a = n_ap: A and Ac stack one image per A' (pairs); 0 or 1: one shared A.
+        sim_k = K > 0: sim is the device address of the (N_A, K) int32 similarity sets (k-coherence search)."""
+        return self.synthesize_levels_device(ch, n_ap, a_hw, b_hw, [ptrs], [kappa_factor], stats, n_a=n_a, sim=sim,
+                                             sim_k=sim_k)
 
-    def synthesize_levels_device(self, ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, stats=None, n_a=0):
+    def synthesize_levels_device(self, ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, stats=None, n_a=0, sim=None, sim_k=0):
         """ia_synthesize_levels on device pointers: one ptrs dict per job (the A-side addresses
         must be equal in all of them), one kappa factor per job; n_a as in synthesize_level_device,
-        or a list with one value per job (the library refuses jobs that differ)."""
+        or a list with one value per job (the library refuses jobs that differ).  sim / sim_k: the A side's
+        similarity sets on the device, for every job (synthesize_level_device)."""
         args = []
         n_as = list(n_a) if isinstance(n_a, (list, tuple)) else [n_a] * len(ptr_list)
         for ptrs, kf, na in zip(ptr_list, kappa_factors, n_as):
@@ -410,11 +431,16 @@ class Context(object):
                                   p['s_out'], p['im_out'], IA_MEM_DEVICE, None, None, int(na)))
         arr = (LevelArgs * len(args))(*args)
         st = stats if stats is not None else Stats()
-        check(lib().ia_synthesize_levels(self._h, arr, len(args), ctypes.byref(st)), 'ia_synthesize_levels')
+        if sim is None and not sim_k:
+            check(lib().ia_synthesize_levels(self._h, arr, len(args), ctypes.byref(st)), 'ia_synthesize_levels')
+        else:
+            check(lib().ia_synthesize_levels_kcoh(self._h, arr, len(args), None if sim is None else ctypes.c_void_p(int(sim)),
+                                                  int(sim_k), ctypes.byref(st)), 'ia_synthesize_levels_kcoh')
         return st
 
 
 KNN_MAX = 64  # IA_KNN_MAX of include/ia.h
+KCOH_MAX = 15  # IA_KCOH_MAX
 
 
 class ExactIndex(object):
@@ -450,6 +476,14 @@ class ExactIndex(object):
         dist = np.empty((q.shape[0], max(k, 0)), dtype=np.float64)
         check(lib().ia_index_query_knn(self._h, _ptr(q), q.shape[0], k, _ptr(idx), _ptr(dist)), 'ia_index_query_knn')
         return idx, dist
+
+    def similarity(self, K):
+        """ia_index_similarity: (n, K) int32, row j = the K rows most similar to row j under query_knn's
+        order, j itself left out (the similarity sets of k-coherence search); 1 <= K <= min(KCOH_MAX, n - 1)."""
+        K = int(K)
+        sim = np.empty((self.n, max(K, 0)), dtype=np.int32)
+        check(lib().ia_index_similarity(self._h, K, _ptr(sim)), 'ia_index_similarity')
+        return sim
 
     def knn_stats(self):
         """ia_index_knn_stats of the last query_knn: (rows whose exact fp64 distance was computed,

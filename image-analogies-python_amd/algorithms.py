@@ -180,6 +180,42 @@ def create_index(A_pyr, Ap_pyr_list, c):
     return flann, flann_params, As, As_size
 
 
+def level_rows(A_pyr, Ap_pyr_list, c, level):
+    """create_index's As[level] alone: [A full feature | A'_i half feature] stacked over the A' images."""
+    two = lambda pyr: [pyr[level - 1], pyr[level]]   # compute_feature_array reads levels l - 1 and l
+    A_list = A_pyr if is_pyramid_list(A_pyr) else [A_pyr] * len(Ap_pyr_list)
+    if len(A_list) != len(Ap_pyr_list):
+        raise ValueError("a list of A pyramids needs one per A' pyramid (got %d for %d)" % (len(A_list), len(Ap_pyr_list)))
+    return np.vstack([np.hstack([compute_feature_array(two(a), c, True)[1], compute_feature_array(two(p), c, False)[1]])
+                      for a, p in zip(A_list, Ap_pyr_list)])
+
+
+def build_similarity(A_pyr, Ap_pyr_list, c, ctx=None):
+    """The similarity sets of k-coherence search, {level: (N_A, K) int32}, for every
+    level 1..max_levels-1 whose DB has at least c.kcoh_min_rows rows (and more than one): an exact
+    K-NN of the level's DB rows against themselves on the GPU (ExactIndex.similarity), K =
+    min(c.kcoh_k, N_A - 1).  Empty when c.kcoh_k is 0.  They depend on the A side alone, so one
+    result serves every job on it (synthesize_pyramid(..., sim=...)); levels it leaves out run exactly."""
+    K = int(getattr(c, 'kcoh_k', 0))
+    sims = {}
+    if K <= 0:
+        return sims
+    if K > _native.KCOH_MAX:
+        raise ValueError('kcoh_k must be 0..%d (got %d)' % (_native.KCOH_MAX, K))
+    L = c.max_levels if getattr(c, 'max_levels', None) else len(Ap_pyr_list[0])
+    for level in range(1, L):
+        h, w = Ap_pyr_list[0][level].shape[:2]
+        n = len(Ap_pyr_list) * h * w
+        if n < max(2, int(getattr(c, 'kcoh_min_rows', 1024))):
+            continue
+        index = _native.ExactIndex(ctx or default_context(), level_rows(A_pyr, Ap_pyr_list, c, level))
+        try:
+            sims[level] = index.similarity(min(K, n - 1))
+        finally:
+            index.close()
+    return sims
+
+
 def best_approximate_match(flann, params, BBp_feat):
     """algorithms.py:73-75 — exact here (see GpuFLANN)."""
     result, dists = flann.nn_index(BBp_feat, 1, checks=params['checks'])

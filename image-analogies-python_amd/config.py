@@ -35,6 +35,9 @@ level_align = 'coarse'  # 'coarse' = reference (image_analogies.py:82-86), 'fine
 seed = None          # np.random seed for initialize_Bp (reference: unseeded global RNG)
 device = None        # HIP device ordinal (None: LOCAL_RANK or 0)
 gpu_preprocess = True  # Gaussian pyramids + YIQ matrices on the GPU (bit-identical to the host code)
+kcoh_k = 0           # K > 0 (<= 15): k-coherence search with K similar rows per DB row: no
+                     # DB scan, NOT the reference's result; 0 = the exact path
+kcoh_min_rows = 1024  # levels with fewer DB rows stay exact when kcoh_k > 0
 
 
 def setup_vars(img):

@@ -123,6 +123,8 @@ struct __attribute__((visibility("hidden"))) ia_ctx {
   DevBuf pr_part, pr_cov, pr_basis, pr_proj, pr_keys, pr_rows, pr_tmp, pos2row, boxes, qinfo, pairs;
   DevBuf qs_order, qs_info, qs_frag, qs_tbox;  // presorted queries of a step (K2s, or the fused gathers' sort)
   DevBuf tnorm;  // per DB tile of a pruned level: R_t >= max |a'| over its rows
+  DevBuf sim;    // k-coherence levels (ia_synthesize_levels_kcoh): the similarity sets of a host-memory call,
+  DevBuf kc_part, kc_cnt;  // ... and their scan waves' minima and counts (ia_kcoh.hip KcohScan)
   DevBuf py_in, py_tmp, py_sm, py_mm, py_out;  // GPU preprocessing (ia_gaussian_pyramid, ia_color_matrix)
   std::vector<double> basis_h;   // staging of the basis upload (lives until the copy ran)
   int64_t prune_min_rows = IA_PRUNE_MIN_ROWS;  // option "prune_min_rows": smallest DB that prunes
@@ -231,7 +233,8 @@ int index_check_queries(const ia_index *x, const std::string &who, const double 
 int index_reserve_batch(ia_index *x, int64_t nq);
 // the merge arguments of an index: its records (x->rec, x->recT, x->qn2 as allocated now) over the whole DB
 MergeArgs index_merge_args(const ia_index *x);
-// per batch of IA_INDEX_BATCH queries: uploads the queries b0 .. b0 + nb to x->q, builds x->qn2 and
+// per batch of IA_INDEX_BATCH queries: uploads the queries b0 .. b0 + nb to x->q (q = nullptr: copies
+// the index's own rows b0 .. b0 + nb there, on the device), builds x->qn2 and
 // x->qf (Mpad = nb padded to qtt query tiles), then body(b0, nb, Mpad, qtt), which enqueues its scans
 // and merge, copies its results and waits for the stream; stops at the first status that is not IA_OK
 int index_for_batches(ia_index *x, const double *q, int64_t nq, const std::function<int(int64_t, int, int, int)> &body);

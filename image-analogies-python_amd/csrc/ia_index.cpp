@@ -60,7 +60,9 @@ int index_for_batches(ia_index *x, const double *q, int64_t nq, const std::funct
   ia_ctx *c = x->ctx;
   for (int64_t b0 = 0; b0 < nq; b0 += IA_INDEX_BATCH) {
     const int nb = (int)std::min(IA_INDEX_BATCH, nq - b0), Mpad = (int)tile_pad(nb);
-    HIP_TRY(hipMemcpyAsync(x->q.p, q + b0 * x->d, (size_t)nb * x->d * 8, hipMemcpyHostToDevice, c->st));
+    if (q) HIP_TRY(hipMemcpyAsync(x->q.p, q + b0 * x->d, (size_t)nb * x->d * 8, hipMemcpyHostToDevice, c->st));
+    else  // the index's own rows b0 .. b0 + nb (ia_index_similarity)
+      HIP_TRY(hipMemcpyAsync(x->q.p, x->pts.as<double>() + b0 * x->d, (size_t)nb * x->d * 8, hipMemcpyDeviceToDevice, c->st));
     ia_launch_dense_query(x->KH, x->q.as<double>(), nb, x->d, Mpad, x->mu.as<double>(), x->sc, x->qn2.as<double>(),
                           x->qf.as<float>(), c->st);
     if (int rc = body(b0, nb, Mpad, Mpad / IA_TILE)) return rc;
@@ -309,6 +311,42 @@ int ia_index_knn_stats(const ia_index *x, int64_t out[2]) {
   out[0] = (int64_t)x->knn_stats[0];
   out[1] = (int64_t)x->knn_stats[1];
   return IA_OK;
+}
+
+// the similarity sets of k-coherence search: the (K + 1)-NN of the index's own rows (the k-NN call's
+// batches, scans, merge and buffers), each row's own entry deleted on the host
+int ia_index_similarity(ia_index *x, int K, int32_t *sim_out) {
+  if (!x || !sim_out) return fail(IA_EINVAL, "ia_index_similarity: NULL argument");
+  if (K < 1 || K > IA_KCOH_MAX || K > x->n - 1)
+    return fail(IA_EINVAL, "ia_index_similarity: K must be 1.." + std::to_string(std::min<int64_t>(IA_KCOH_MAX, x->n - 1)) +
+                               " (IA_KCOH_MAX and the index's rows - 1)");
+  ia_ctx *c = x->ctx;
+  HIP_TRY(hipSetDevice(c->dev));
+  const int k = K + 1;
+  const int64_t nq = x->n, bmax = std::min(nq, IA_INDEX_BATCH);
+  int rc;
+  if ((rc = index_reserve_batch(x, nq)) || (rc = x->rec.ensure((size_t)bmax * x->nwg * 16)) ||
+      (rc = x->recT.ensure((size_t)bmax * x->nwg * 4)) ||
+      (rc = x->idx.ensure((size_t)bmax * k * 8)) || (rc = x->dist.ensure((size_t)bmax * k * 8)))
+    return rc;
+  HIP_TRY(hipMemsetAsync(x->counters.p, 0, 32, c->st));
+  const MergeArgs ma = index_merge_args(x);
+  std::vector<int64_t> nn((size_t)bmax * k);
+  return index_for_batches(x, nullptr, nq, [&](int64_t b0, int nb, int, int qtt) -> int {
+    index_scan_top2(x, nb, qtt);
+    ia_launch_merge_dense_knn(ma, x->pts.as<double>(), x->d, x->q.as<double>(), nb, k, x->sc * x->sc, x->idx.as<int64_t>(),
+                              x->dist.as<double>(), x->counters.as<unsigned long long>(), c->st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(nn.data(), x->idx.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    for (int i = 0; i < nb; i++) {
+      int32_t *o = sim_out + (b0 + i) * K;
+      int n_out = 0;
+      for (int j = 0; j < k && n_out < K; j++)
+        if (nn[(size_t)i * k + j] != b0 + i) o[n_out++] = (int32_t)nn[(size_t)i * k + j];
+    }
+    return IA_OK;
+  });
 }
 
 int ia_coherence_batch(ia_index *x, const double *q, int64_t nq, const int32_t *px, const int32_t *s, const int32_t *im,

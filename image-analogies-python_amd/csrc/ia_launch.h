@@ -1,6 +1,6 @@
 // ia_launch.h — host launchers of the kernels in ia_level_db.hip, ia_gather.hip, ia_k3.hip,
 // ia_kernels.hip (the per-step merges), ia_merge_shard.hip, ia_dense.hip, ia_k3r.hip, ia_prune.hip,
-// ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
+// ia_kcoh.hip, ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
 // ia_k3.hip and ia_k3r.hip scan with one body (ia_k3_scan.h): ia_launch_k3, ia_launch_k3r_count and
 // ia_launch_k3r_fill take the same geometry (n_tiles, tpw, nwg; qt <= ia_k3_qtmax(KH) tiles from qt0).
 #pragma once
@@ -119,6 +119,14 @@ struct K3pLaunch {
 };
 // returns IA_EINVAL (nothing launched) when no kernel instance exists for the variant
 int ia_launch_k3p(const K3pLaunch &a, int option, bool presorted, hipStream_t st);
+// k-coherence search (ia_kcoh.hip): one wavefront step of a level with similarity sets sim
+// (NA x K rows), all jobs, with H = ia_kcoh_scan_waves(NA) scan waves for the pixels without a base
+// row (part: 16 H bytes per query of the widest step; cnt: one word per query, zero between steps);
+// and the pre-pass that sets *err when one of sim's n entries is no DB row
+int ia_kcoh_scan_waves(int64_t NA);
+void ia_launch_kcoh_step(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const Imgs &B, const JobSet &jobs,
+                         const double *db64, const int32_t *sim, int K, int H, void *part, unsigned *cnt, hipStream_t st);
+void ia_launch_kcoh_check(const int32_t *sim, int64_t n, int NA, unsigned *err, hipStream_t st);
 // GPU preprocessing (ia_pyramid.hip)
 void ia_launch_pyramid_reduce(const double *in, double *out, double *tmp, double *sm, double *mm, int h, int w, int ch,
                               const double *w7, hipStream_t st);

@@ -147,5 +147,6 @@ int build_level_db(ia_ctx *c, LevelPlan &P, const LevelInputs &in, double *ufac)
 // the level's ia_stats (ia_level_stats.cpp): n_gm sampled steps' gather / merge brackets
 int accumulate_stats(ia_ctx *c, const LevelPlan &P, const StampSlots &stamps, const ScanTally &tally, int64_t n_gm,
                      double gather_bytes_timed, ia_stats *stats);
+int accumulate_kcoh_stats(ia_ctx *c, const LevelPlan &P, ia_stats *stats);  // a k-coherence level's
 
 }  // namespace ia_host

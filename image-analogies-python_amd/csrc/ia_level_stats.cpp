@@ -200,4 +200,36 @@ int accumulate_stats(ia_ctx *c, const LevelPlan &P, const StampSlots &stamps, co
   return IA_OK;
 }
 
+// a k-coherence level (no scan, no tiles): the pixel counters - the stats words carry the
+// candidates where K4 counts reranks and the fallback pixels where it counts rescanned chunks -
+// and the level's two event brackets (K1b is the whole DB build)
+int accumulate_kcoh_stats(ia_ctx *c, const LevelPlan &P, ia_stats *stats) {
+  const LevelGeo &g = P.g;
+  unsigned long long ctr[5];
+  HIP_TRY(hipMemcpy(ctr, c->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));
+  float ms_db = 0.f, ms_syn = 0.f;
+  hipEventElapsedTime(&ms_db, c->lv0, c->lv1);
+  hipEventElapsedTime(&ms_syn, c->lv1, c->lv2);
+  if (g.NA >= stats->build_rows) {
+    if (g.NA > stats->build_rows) {
+      stats->k1b_ms = stats->k1b_bytes = stats->k1_ms = stats->k1_bytes = 0.;
+      stats->build_levels = 0;
+      stats->build_rows = g.NA;
+    }
+    stats->k1b_ms += ms_db;
+    stats->k1b_bytes += (double)(P.nA + P.nAc) * (g.n_a + g.n_ap) * 8 + (double)g.NA * ia_db64_stride(g.ch) * 8;
+    stats->build_levels += 1;
+  }
+  stats->pixels += P.NB * P.J;
+  stats->steps += P.T;
+  stats->kcoh_levels += P.J;
+  stats->kcoh_candidates += (int64_t)ctr[0];
+  stats->kcoh_fallbacks += (int64_t)ctr[1];
+  stats->coherence_wins += (int64_t)ctr[2];
+  stats->kappa_ambiguous += (int64_t)ctr[4];
+  stats->db_ms += ms_db;
+  stats->synth_ms += ms_syn;
+  return IA_OK;
+}
+
 }  // namespace ia_host

@@ -18,7 +18,7 @@ import warnings
 import numpy as np
 
 from . import _native
-from .algorithms import a_levels, default_context
+from .algorithms import a_levels, build_similarity, default_context
 from .config import save_metadata, setup_vars
 from .img_preprocess import (compress_values, compute_gaussian_pyramid, convert_to_RGB, convert_to_YIQ,
                              initialize_Bp, remap_luminance)
@@ -119,17 +119,25 @@ def check_windows(c):
                          'got n_sm = %r, n_lg = %r, n_half = %r)' % (n_sm, n_lg, getattr(c, 'n_half', None)))
 
 
-def synthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, c, ctx=None, stats=None, on_level=None, debug=None):
+def synthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, c, ctx=None, stats=None, on_level=None, debug=None, sim=None):
     """The level loop of image_analogies_main (image_analogies.py:130-239) on the GPU.
     Bp_pyr levels 1..max_levels-1 are synthesised in place; returns ({level: s}, {level: im}).
     debug: a dict that receives {level: {'src', 'dist'}} per-pixel debug records
     (_native.Context.synthesize_level).
     A_pyr: one pyramid, or a list of pyramids with one per A' (algorithms.is_pyramid_list).
     Warns when a kappa decision sat where libm's pow (the reference's `** 2`) could round the
-    other way than the kernel's y * y (ia_stats.kappa_ambiguous; 0 on every fixture)."""
+    other way than the kernel's y * y (ia_stats.kappa_ambiguous; 0 on every fixture).
+    sim: {level: similarity sets} (algorithms.build_similarity): those levels run by k-coherence
+    search, the others exactly; None: computed here when c.kcoh_k > 0 (for the levels with at least
+    c.kcoh_min_rows DB rows), else every level is exact.  A k-coherence level is not the reference's
+    result and takes no debug records."""
     check_windows(c)
     ctx = ctx or default_context()
     L = c.max_levels
+    if sim is None:
+        sim = build_similarity(A_pyr, Ap_pyr_list, c, ctx) if getattr(c, 'kcoh_k', 0) else {}
+    if debug is not None and sim:
+        raise ValueError('debug records are produced by exact levels only: set kcoh_k = 0 (or pass sim={})')
     S, IM = {}, {}
     stats = stats if stats is not None else _native.Stats()
     amb0 = stats.kappa_ambiguous
@@ -140,7 +148,8 @@ def synthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, c, ctx=None, stats=Non
         S[level], IM[level] = ctx.synthesize_level(
             a_levels(A_pyr, level), a_levels(A_pyr, level - 1), [p[level] for p in Ap_pyr_list],
             [p[level - 1] for p in Ap_pyr_list],
-            B_pyr[level], B_pyr[level - 1], Bp_pyr[level - 1], Bp_pyr[level], c.weights, kf, stats, debug=dbg)
+            B_pyr[level], B_pyr[level - 1], Bp_pyr[level - 1], Bp_pyr[level], c.weights, kf, stats, debug=dbg,
+            sim=sim.get(level))
         if on_level is not None:
             on_level(level, S, IM)
     if stats.kappa_ambiguous > amb0:

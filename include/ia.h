@@ -113,6 +113,11 @@ typedef struct {
   double k3p_bytes_unique_all; /* k3p_bytes_all with each launch's DB tiles counted at most once
                                 * (<= the launch's whole tiles): launches of several query blocks
                                 * stream a tile once per block (cfg4's wide steps) */
+  /* k-coherence levels (ia_synthesize_levels_kcoh) */
+  int64_t kcoh_levels;      /* levels (jobs) run by k-coherence search */
+  int64_t kcoh_fallbacks;   /* their pixels without a base row: exact NN over the whole DB */
+  int64_t kcoh_candidates;  /* candidate rows (base rows and their similar rows) whose exact
+                             * distance was computed; a fallback pixel's DB scan is not counted */
 } ia_stats;
 
 /* One pyramid level (image_analogies.py:130-239).  Shapes: A/A' level l is (a_h, a_w[, ch]),
@@ -161,7 +166,8 @@ typedef struct {
 int ia_init(int device, ia_ctx **out);
 void ia_destroy(ia_ctx *ctx);
 const char *ia_last_error(void);
-int ia_version(void);  /* 2: ia_level_args.n_a (1: the struct ended at dbg_dist) */
+int ia_version(void);  /* 3: ia_synthesize_levels_kcoh, ia_index_similarity, ia_stats.kcoh_*; 2: ia_level_args.n_a
+                        * (1: the struct ended at dbg_dist) */
 /* Options: "time_dist" = S (0 = off): bracket the MFMA distance launches of every S-th
  * wavefront step with HIP events; ia_stats.dist_ms / dist_flops_timed then give the kernel's
  * measured device time and algorithmic flops (bench.py roofline).
@@ -289,6 +295,27 @@ int ia_synthesize_level(ia_ctx *ctx, const ia_level_args *args, ia_stats *stats)
  * ia_synthesize_level calls, bit for bit.  1 <= n_jobs <= 32.  Sharded levels take batches too
  * ("exchange" 0 / 1: every rank holds every job; emulated "exchange" = 2: one job per shard). */
 int ia_synthesize_levels(ia_ctx *ctx, const ia_level_args *args, int n_jobs, ia_stats *stats);
+/* The same call by k-coherence search: the level runs without a DB scan.  sim_k = K
+ * in 1..min(IA_KCOH_MAX, N_A - 1), N_A = n_ap a_h a_w; sim is N_A x K int32 in the memory kind
+ * args[0].mem names, like every pointer of the jobs: sim[j] = the K DB rows most similar to row j
+ * (ia_index_similarity on the level's rows).  The sets belong to the A side, so one serves every job
+ * of the batch.  Per pixel q = (r, c) in raster order the base rows are the shifted sources of its
+ * causal neighbours (best_coherence_match's cells: rows r-2..r x cols c-2..c+2, raster-earlier,
+ * source + q - r' inside A); the candidates are every base row b and sim[b][0..K); p_app = the
+ * candidate with the smallest (exact fp64 distance in numpy's pairwise order, row index).
+ * best_coherence_match, the kappa rule and the writeback are unchanged.  A pixel without a base row
+ * (always the level's first) takes the exact NN over the whole DB and has no coherence candidate,
+ * as on the exact path.  With K = N_A - 1 the level equals ia_synthesize_levels bit for bit;
+ * otherwise it is NOT the reference's result.  sim_k = 0 (sim ignored) is ia_synthesize_levels.
+ * (ia_level_args keeps its version-2 layout: the sets travel as arguments of their own.)
+ * IA_EINVAL, before any step runs and with nothing written: sim_k outside 0..IA_KCOH_MAX or above
+ * N_A - 1, sim NULL with sim_k > 0, a sim entry outside [0, N_A) (one pre-pass kernel), debug
+ * buffers, a context that is a rank of a shard (ia_comm_init / ia_xchg_open with world > 1) or
+ * emulates one ("shard_emulate" > 1), a context with "pipeline_record" = 1 or a pending
+ * ia_pipeline_depend (which the refused call consumes). */
+#define IA_KCOH_MAX 15
+int ia_synthesize_levels_kcoh(ia_ctx *ctx, const ia_level_args *args, int n_jobs, const int32_t *sim, int sim_k,
+                              ia_stats *stats);
 
 /* Level pipelining: level l + 1 of a job only reads B' of level l near
  * (r / 2, c / 2), so its wavefront step t needs level l's steps <= t / 2 + 4, not the whole level.
@@ -327,6 +354,13 @@ int ia_index_query_knn(ia_index *index, const double *q, int64_t nq, int k, int6
  * distance was computed (reranked candidates + rows of rescanned chunks; a brute force computes
  * nq x n), out[1] = scan chunks rescanned exactly. */
 int ia_index_knn_stats(const ia_index *index, int64_t out[2]);
+/* Similarity sets of the index's own rows (k-coherence search, ia_synthesize_levels_kcoh): for row j the
+ * K + 1 nearest rows under ia_index_query_knn's order, the entry equal to j deleted if present,
+ * the first K of what remains.  Duplicates of row j with lower indices come before j and stay.
+ * The queries are the rows the index holds on the device, in ia_index_query_knn's batches and
+ * workspace.  sim_out: n x K int32, host memory.  IA_EINVAL (nothing written) for K outside
+ * 1..min(IA_KCOH_MAX, n - 1) or a NULL argument. */
+int ia_index_similarity(ia_index *index, int K, int32_t *sim_out);
 /* nn_radius(q, radius): exact fixed-radius search under the same distance (pyflann's radius is a
  * squared distance too).  radius holds nq values, one per query, each >= 0 and not NaN; +inf means
  * every row.  A row is inside when dist < radius, strictly: radius 0 returns nothing, even for an
