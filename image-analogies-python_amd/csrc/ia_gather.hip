@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(IA_PQ_WG) k_gather_query_p(LevelGeo g, StepDes
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launchers (called from ia_level_run.cpp)
+// host-side launchers (called from ia_level_run.cpp, ia_level_owner.cpp)
 // ------------------------------------------------------------------------------------------
 void ia_launch_gather(const LevelGeo &g, const StepDesc &sd, const Imgs &B, const JobSet &jobs, const double *mu, double *q64,
                       double *qn2, float *qf, hipStream_t st) {

@@ -669,7 +669,7 @@ k_merge_gather(LevelGeo g, StepDesc sd, Imgs A, MergeArgs ma, JS jobs, Imgs B, N
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launchers (called from ia_level_run.cpp)
+// host-side launchers (called from ia_level_run.cpp, ia_level_owner.cpp)
 // ------------------------------------------------------------------------------------------
 void ia_launch_merge(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const MergeArgs &ma, Winner *win,
                      const JobSet &jobs, bool fused, hipStream_t st) {

@@ -1,7 +1,11 @@
 // ia_level.h — what the phases of a level call (ia_synthesize_levels) hand to each other: the
-// plan, the staged inputs, the stamp slots and the scan tally, and the phase functions that
-// ia_level_plan.cpp and ia_level_stats.cpp define for the step loop in ia_level_run.cpp.
+// plan, the staged inputs, a step's descriptor, the stamp slots, the scan tally and the link
+// between pipelined levels, and the phase functions that ia_level_plan.cpp, ia_level_stats.cpp
+// and ia_level_kcoh.cpp define for the level call in ia_level_run.cpp (its steps: ia_level_run.h).
 #pragma once
+#include <chrono>
+#include <thread>
+
 #include "ia_host.h"
 
 namespace ia_host __attribute__((visibility("hidden"))) {
@@ -47,6 +51,98 @@ struct LevelInputs {
 };
 
 // ---- what the steps share -------------------------------------------------------------------
+// Step t of the level for J jobs stepped together (J = 1: one owner's view of a batched step).
+// M <= 0: the step holds no query (levels narrower than 3 columns); the callers skip it.
+inline StepDesc step_desc(const LevelGeo &g, int64_t t, int J) {
+  StepDesc sd{(int)t, 0, 0, 0, J};
+  ia_wavefront_step(g.bh, g.bw, t, &sd.r0, &sd.M);
+  sd.Mpad = (int)tile_pad(J * sd.M);
+  return sd;
+}
+
+// Level pipelining: this level's per-step events (a recording context) and its
+// waits on the level before it (ia_pipeline_depend).  Every return after open() - errors too -
+// releases the dependents' waits (p_done).
+struct PipelineLink {
+  ia_ctx *c = nullptr;
+  int gen = 0;                      // this call's generation (0: not recording)
+  std::vector<hipEvent_t> *pev = nullptr;
+  bool no_events = false;           // option "pipeline_last": nothing waits on this call's steps
+  ia_ctx *dp = nullptr;             // the context of the level before, its generation
+  int dgen = 0;
+  int64_t waited = -1;
+  // the previous level's host thread stopped enqueueing (it failed): 120 s without progress of
+  // its generation or its enqueued steps (a long but healthy predecessor keeps resetting this)
+  std::chrono::steady_clock::time_point t_prog;
+  long long seen_enq = -2;
+  int seen_gen = -1;
+
+  int open(ia_ctx *ctx, int64_t T) {
+    c = ctx;
+    const int g = c->p_record ? c->p_gen.load() + 1 : 0;
+    if (g) {
+      pev = &c->p_ev[g % 3];
+      while ((int64_t)pev->size() < T) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        pev->push_back(e);
+      }
+      c->p_enq.store(-1);
+      c->p_T.store(T);
+      c->p_gen.store(g);  // published last: a dependent reads p_T / p_enq of this generation after it
+    }
+    gen = g;
+    dp = c->dep;
+    dgen = c->dep_gen;
+    c->dep = nullptr;  // one level call per ia_pipeline_depend
+    c->dep_gen = 0;
+    t_prog = std::chrono::steady_clock::now();
+    no_events = c->p_last != 0;
+    c->p_last = 0;
+    return IA_OK;
+  }
+  ~PipelineLink() {
+    if (gen) c->p_done.store(gen);
+  }
+  bool stalled() {
+    const auto now = std::chrono::steady_clock::now();
+    const long long e = dp->p_enq.load();
+    const int gn = dp->p_gen.load();
+    if (e != seen_enq || gn != seen_gen) {
+      seen_enq = e;
+      seen_gen = gn;
+      t_prog = now;
+      return false;
+    }
+    return now - t_prog > std::chrono::seconds(120);
+  }
+  // step t reads B' of the previous level's steps <= t / 2 + 4
+  int wait_dep(int64_t t) {
+    if (!dp) return IA_OK;
+    while (dp->p_gen.load() < dgen && dp->p_done.load() < dgen)  // it has started that level
+      if (stalled()) return fail(IA_ECOMM, "pipeline: the previous level did not start");
+      else std::this_thread::yield();
+    const int64_t need = std::min<int64_t>(t / 2 + 4, dp->p_T.load() - 1);
+    if (need <= waited) return IA_OK;
+    while (dp->p_done.load() < dgen && dp->p_enq.load() < need)
+      if (stalled()) return fail(IA_ECOMM, "pipeline: the previous level stopped enqueueing");
+      else std::this_thread::yield();
+    if (dp->p_done.load() < dgen) {
+      hipEvent_t ev = dp->p_ev[dgen % 3][need];
+      // the previous level usually runs far ahead: an event that already completed needs no
+      // barrier packet on this stream
+      if (hipEventQuery(ev) != hipSuccess) HIP_TRY(hipStreamWaitEvent(c->st, ev, 0));
+    }
+    waited = need;
+    return IA_OK;
+  }
+  void mark_step(int64_t t) {
+    if (!gen) return;
+    if (!no_events) hipEventRecord((*pev)[t], c->st);
+    c->p_enq.store(t);
+  }
+};
+
 // Option "stamps" (pruned levels): per-launch workgroup stamps of every K3p launch (<= IA_NWG_H
 // workgroups each) and every fused merge launch (<= Mpad_max + J + 1 workgroups).  The slots
 // start zeroed (fresh buffers here), and the slots a level wrote are cleared on EVERY exit
@@ -148,5 +244,15 @@ int build_level_db(ia_ctx *c, LevelPlan &P, const LevelInputs &in, double *ufac)
 int accumulate_stats(ia_ctx *c, const LevelPlan &P, const StampSlots &stamps, const ScanTally &tally, int64_t n_gm,
                      double gather_bytes_timed, ia_stats *stats);
 int accumulate_kcoh_stats(ia_ctx *c, const LevelPlan &P, ia_stats *stats);  // a k-coherence level's
+
+// phase 5 (ia_level_run.cpp): the stats words' reduction, the D2H copies of host-memory jobs, the
+// level's one sync, and the error word of the handoffs (chain) and exchanges
+int finish_level(ia_ctx *c, const ia_level_args *args, const LevelPlan &P, const LevelInputs &in, bool chain, bool want_stats);
+
+// k-coherence levels (ia_level_kcoh.cpp): what the sets, the context and the batch must be for
+// one, and the level after plan_shards and stage_level
+int check_kcoh(ia_ctx *c, const ia_level_args *args, int J, const int32_t *sim, int sim_k);
+int run_kcoh_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const int32_t *sim_in, int K,
+                   ia_stats *stats);
 
 }  // namespace ia_host

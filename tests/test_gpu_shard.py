@@ -263,3 +263,54 @@ def test_owner_shards_with_unequal_tile_counts(ctx, presort):
         for level in range(1, z['L']):
             assert np.array_equal(Bp[n][level], Bpu[n][level]), (n, level)
     assert st.bound_violations == 0 and st.dist_launches > stu.dist_launches
+
+
+def test_owner_steps_cross_the_inkernel_sort_limit(ctx):
+    """One owner-computes level (exchange = 2, W = 2, fused gather on) whose steps cross the in-kernel
+    sort's limit in both directions: B 353 x 1063 has steps of 353 queries per owner (12 query tiles,
+    above one launch's 11: sorted through K2s) between steps of <= 352 (sorted in the scan).  The
+    fused merge before the first wide step must not publish its next queries, the one after the last
+    must again.  A / A' 64 x 64 = 128 tiles, the smallest DB that shards two ways; two jobs (other B,
+    other kappa) == the same jobs batched unsharded."""
+    from golden_util import PRUNE_MIN_ROWS_DEFAULT, QTMAX
+    from ia_amd import _native, synth
+    jobs = synth.make_jobs(2, size=64, b_size=(353, 1063), n_levels=2)
+    j0 = jobs[0]
+    assert j0.L == 2 and j0.A_pyr[1].shape == (64, 64) and j0.A_pyr[0].shape == (32, 32)
+    h, w = j0.B_pyr[1].shape
+    assert (h, w) == (353, 1063)
+    limit = QTMAX['f16x3', 1] * 32   # queries per owner that one scan launch sorts itself
+    T, _ = _native.wavefront_shape(h, w)
+    ink = [-(-m // 32) * 32 <= limit for m in (_native.wavefront_step(h, w, t)[1] for t in range(T))]
+    wide = [t for t in range(T) if not ink[t]]
+    assert wide and ink[wide[0] - 1] and ink[wide[-1] + 1] and wide[0] > 1 and wide[-1] < T - 2
+    kappa = (j0.kappa_factor(1), 1 + 0.5 * 25.0)
+    out = []
+    ctx.set_option('prune_min_rows', 1)
+    ctx.set_option('xo_presort', 0)
+    try:
+        for Wx, ex in ((2, 2), (1, 0)):
+            st = _native.Stats()
+            ctx.set_option('shard_emulate', Wx)
+            ctx.set_option('exchange', ex)
+            Bp = [[x.copy() for x in j.Bp_init] for j in jobs]
+            specs = [dict(B=j.B_pyr[1], Bc=j.B_pyr[0], Bpc=Bp[n][0], Bp=Bp[n][1], weights=j.weights, kappa_factor=kappa[n])
+                     for n, j in enumerate(jobs)]
+            res = ctx.synthesize_levels(j0.A_pyr[1], j0.A_pyr[0], [p[1] for p in j0.Ap_pyr_list],
+                                        [p[0] for p in j0.Ap_pyr_list], specs, st)
+            out.append((res, Bp, st))
+    finally:
+        ctx.set_option('shard_emulate', 1)
+        ctx.set_option('exchange', 0)
+        ctx.set_option('xo_presort', 0)
+        ctx.set_option('prune_min_rows', PRUNE_MIN_ROWS_DEFAULT)
+    (res, Bp, st), (resu, Bpu, stu) = out
+    for n in range(2):
+        assert np.array_equal(res[n][0], resu[n][0]) and np.array_equal(res[n][1], resu[n][1]), n
+        assert np.array_equal(Bp[n][1], Bpu[n][1]), n
+    assert not np.array_equal(jobs[0].B_pyr[1], jobs[1].B_pyr[1])
+    print(len(wide), wide[0], wide[-1], T, st.pruned_levels, stu.pruned_levels, st.dist_launches, stu.dist_launches)
+    # one pruned level: the counter adds one per job of it (ia_level_stats.cpp), as in
+    # test_emulated_shards_batched_1024
+    assert st.bound_violations == 0 and st.pruned_levels == 1 * len(jobs)
+    assert stu.bound_violations == 0 and stu.pruned_levels == 1 * len(jobs)
