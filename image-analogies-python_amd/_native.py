@@ -61,7 +61,8 @@ class Stats(ctypes.Structure):
                 ('k3p_stamp_start_ms', ctypes.c_double), ('k3p_stamp_wg_ms', ctypes.c_double),
                 ('stamp_gap_sm_ms', ctypes.c_double), ('stamp_gaps_sm', ctypes.c_int64),
                 ('k3p_bytes_unique_all', ctypes.c_double),
-                ('kcoh_levels', ctypes.c_int64), ('kcoh_fallbacks', ctypes.c_int64), ('kcoh_candidates', ctypes.c_int64)]
+                ('kcoh_levels', ctypes.c_int64), ('kcoh_fallbacks', ctypes.c_int64), ('kcoh_candidates', ctypes.c_int64),
+                ('nbhd_levels', ctypes.c_int64)]
 
     # fields that describe only the levels with the largest DB seen (build_rows / prune_rows)
     _BUILD = ('k1b_ms', 'k1b_bytes', 'k1_ms', 'k1_bytes', 'build_levels')
@@ -99,6 +100,8 @@ EXPORTS = {
     'ia_xchg_alloc': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p]),
     'ia_xchg_open': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]),
     'ia_synthesize_levels_kcoh': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LevelArgs), ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_int, ctypes.POINTER(Stats)]),
+    'ia_synthesize_levels_nbhd': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LevelArgs), ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, ctypes.POINTER(Stats)]),
     'ia_pipeline_depend': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     'ia_pipeline_generation': (ctypes.c_int, [ctypes.c_void_p]),
@@ -138,6 +141,10 @@ EXPORTS = {
                                           ctypes.POINTER(ctypes.c_int64)]),
     'ia_wavefront_step': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int),
                                          ctypes.POINTER(ctypes.c_int)]),
+    'ia_wavefront_shape_pad': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
+                                              ctypes.POINTER(ctypes.c_int64)]),
+    'ia_wavefront_step_pad': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     'ia_shard_tiles': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                       ctypes.POINTER(ctypes.c_int64)]),
     'ia_shard_tiles_pruned': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int,
@@ -205,10 +212,19 @@ def stack_pairs(A_list, Ac_list, n_ap):
     return _c64(np.stack(A_list)), _c64(np.stack(Ac_list))
 
 
-def check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w):
+NBHD_N_SM, NBHD_N_LG, NBHD_MAX_D = (1, 3, 5), (3, 5, 7, 9), 167   # ia_synthesize_levels_nbhd's sizes (include/ia.h)
+
+
+def feature_width(n_sm, n_lg, ch):
+    """D of a DB row with n_sm x n_sm coarse and n_lg x n_lg fine windows: ch (2 n_sm^2 + n_lg^2 + n_lg^2 // 2)"""
+    return ch * (2 * n_sm * n_sm + n_lg * n_lg + (n_lg * n_lg) // 2)
+
+
+def check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w, windows=(3, 5)):
     """The C ABI derives every size from A's channel count and B's shape (include/ia.h
     ia_level_args); check the rest here so a mismatched call raises instead of reading or
-    writing past a host buffer.  Ap / Apc are the stacked A' images.  Returns ch."""
+    writing past a host buffer.  Ap / Apc are the stacked A' images.  windows: the level's
+    (n_sm, n_lg), which set the weights' length.  Returns ch."""
     if A.ndim not in (2, 3):
         raise IAError('A must be (h, w) or (h, w, ch)')
     ch = 1 if A.ndim == 2 else A.shape[2]
@@ -228,8 +244,13 @@ def check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w):
             raise IAError('%s must be the coarser level of B, %s (got %s)' % (name, half(B), x.shape))
     if Bp.shape != B.shape:
         raise IAError("Bp must have B's shape %s (got %s)" % (B.shape, Bp.shape))
-    if w.shape != (55 * ch,):
-        raise IAError('weights must have 55 * ch = %d entries (3x3 / 5x5 windows; got %s)' % (55 * ch, w.shape))
+    if tuple(windows) == (3, 5):
+        if w.shape != (55 * ch,):
+            raise IAError('weights must have 55 * ch = %d entries (3x3 / 5x5 windows; got %s)' % (55 * ch, w.shape))
+    elif w.shape != (feature_width(windows[0], windows[1], ch),):
+        raise IAError('weights must have %d entries (%dx%d / %dx%d windows, %d channels; got %s)'
+                      % (feature_width(windows[0], windows[1], ch), windows[0], windows[0], windows[1], windows[1], ch,
+                         w.shape))
     return ch
 
 
@@ -331,7 +352,7 @@ class Context(object):
         return lib().ia_pipeline_generation(self._h)
 
     def synthesize_level(self, A, Ac, Ap_list, Apc_list, B, Bc, Bpc, Bp, weights, kappa_factor, stats=None,
-                         debug=None, sim=None):
+                         debug=None, sim=None, windows=None):
         """ia_synthesize_level on host numpy arrays.  A / Ac: one array each (the A every A' shares)
         or lists with one array per A' (pairs (A_i, A'_i) of equal shape; IAShapeError, a
         ValueError, otherwise).  Bp (fp64, C-contiguous) is updated in place
@@ -342,18 +363,26 @@ class Context(object):
         [d_app, d_coh] (image_analogies.py:224-240), finished on the host as numpy does.
         sim: (N_A, K) similarity sets of the level's DB rows (ExactIndex.similarity): the level runs
         by k-coherence search (include/ia.h ia_synthesize_levels_kcoh) - not the reference's result unless
-        K = N_A - 1; None: the exact path."""
+        K = N_A - 1; None: the exact path.
+        windows: (n_sm, n_lg): the level runs through ia_synthesize_levels_nbhd with those window sizes
+        (weights then hold feature_width(n_sm, n_lg, ch) values; no debug, no sim); None: the default
+        call, 3 / 5."""
         job = dict(B=B, Bc=Bc, Bpc=Bpc, Bp=Bp, weights=weights, kappa_factor=kappa_factor, debug=debug)
-        return self.synthesize_levels(A, Ac, Ap_list, Apc_list, [job], stats, sim=sim)[0]
+        return self.synthesize_levels(A, Ac, Ap_list, Apc_list, [job], stats, sim=sim, windows=windows)[0]
 
-    def synthesize_levels(self, A, Ac, Ap_list, Apc_list, jobs, stats=None, sim=None):
+    def synthesize_levels(self, A, Ac, Ap_list, Apc_list, jobs, stats=None, sim=None, windows=None):
         """ia_synthesize_levels: one level of several jobs that share the A side (A, A' levels l and
         l-1), e.g. a kappa / pyramid-depth sweep (multi_script.py).  jobs: list of dicts with
         B, Bc, Bpc, Bp (updated in place), weights, kappa_factor and optionally debug (a dict, see
         synthesize_level).  A / Ac may be lists, one image per A' (pairs), as in synthesize_level.
         One DB, one distance scan per wavefront step for all jobs.  Returns
         [(s, im)] per job, each identical to a separate synthesize_level call.
-        sim: the A side's similarity sets, shared by every job (synthesize_level)."""
+        sim: the A side's similarity sets, shared by every job (synthesize_level).
+        windows: (n_sm, n_lg) for every job, or None (synthesize_level)."""
+        if windows is not None:
+            windows = (int(windows[0]), int(windows[1]))
+            if sim is not None or any(jb.get('debug') is not None for jb in jobs):
+                raise IAError('synthesize_levels: windows= takes neither sim nor debug (ia_synthesize_levels_nbhd)')
         if not 1 <= len(jobs) <= 32:
             raise IAError('synthesize_levels: 1..32 jobs per call (got %d)' % len(jobs))
         Ap = _c64(np.stack(Ap_list))
@@ -376,7 +405,7 @@ class Context(object):
             B, Bc, Bpc, Bp, w = _c64(jb['B']), _c64(jb['Bc']), _c64(jb['Bpc']), jb['Bp'], _c64(jb['weights'])
             if not (isinstance(Bp, np.ndarray) and Bp.dtype == np.float64 and Bp.flags.c_contiguous):
                 raise IAError('Bp must be a C-contiguous float64 array (updated in place)')
-            ch = check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w)
+            ch = check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w, windows=windows or (3, 5))
             bh, bw = B.shape[:2]
             s = np.empty((bh * bw, 2), dtype=np.int32)
             im = np.empty(bh * bw, dtype=np.int32)
@@ -392,7 +421,10 @@ class Context(object):
             outs.append((s, im, dsrc, ddist, jb.get('debug')))
         arr = (LevelArgs * len(args))(*args)
         st = stats if stats is not None else Stats()
-        if sim is None:
+        if windows is not None:
+            check(lib().ia_synthesize_levels_nbhd(self._h, arr, len(args), windows[0], windows[1], ctypes.byref(st)),
+                  'ia_synthesize_levels_nbhd')
+        elif sim is None:
             check(lib().ia_synthesize_levels(self._h, arr, len(args), ctypes.byref(st)), 'ia_synthesize_levels')
         else:
             check(lib().ia_synthesize_levels_kcoh(self._h, arr, len(args), _ptr(sim), sim_k, ctypes.byref(st)),
@@ -409,15 +441,18 @@ class Context(object):
             res.append((s, im))
         return res
 
-    def synthesize_level_device(self, ch, n_ap, a_hw, b_hw, ptrs, kappa_factor, stats=None, n_a=0, sim=None, sim_k=0):
+    def synthesize_level_device(self, ch, n_ap, a_hw, b_hw, ptrs, kappa_factor, stats=None, n_a=0, sim=None, sim_k=0,
+                                windows=None):
         """Same on device pointers (IA_MEM_DEVICE): ptrs = dict of int addresses for
         A, Ac, Ap, Apc, B, Bc, Bpc, Bp, weights, s_out, im_out (e.g. torch tensor data_ptr()).
         n_a = n_ap: A and Ac stack one image per A' (pairs); 0 or 1: one shared A.
-        sim_k = K > 0: sim is the device address of the (N_A, K) int32 similarity sets (k-coherence search)."""
+        sim_k = K > 0: sim is the device address of the (N_A, K) int32 similarity sets (k-coherence search).
+        windows = (n_sm, n_lg): ia_synthesize_levels_nbhd (the weights hold feature_width(n_sm, n_lg, ch) values)."""
         return self.synthesize_levels_device(ch, n_ap, a_hw, b_hw, [ptrs], [kappa_factor], stats, n_a=n_a, sim=sim,
-                                             sim_k=sim_k)
+                                             sim_k=sim_k, windows=windows)
 
-    def synthesize_levels_device(self, ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, stats=None, n_a=0, sim=None, sim_k=0):
+    def synthesize_levels_device(self, ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, stats=None, n_a=0, sim=None, sim_k=0,
+                                 windows=None):
         """ia_synthesize_levels on device pointers: one ptrs dict per job (the A-side addresses
         must be equal in all of them), one kappa factor per job; n_a as in synthesize_level_device,
         or a list with one value per job (the library refuses jobs that differ).  sim / sim_k: the A side's
@@ -431,7 +466,12 @@ class Context(object):
                                   p['s_out'], p['im_out'], IA_MEM_DEVICE, None, None, int(na)))
         arr = (LevelArgs * len(args))(*args)
         st = stats if stats is not None else Stats()
-        if sim is None and not sim_k:
+        if windows is not None:
+            if sim is not None or sim_k:
+                raise IAError('synthesize_levels_device: windows= takes no sim (ia_synthesize_levels_nbhd)')
+            check(lib().ia_synthesize_levels_nbhd(self._h, arr, len(args), int(windows[0]), int(windows[1]), ctypes.byref(st)),
+                  'ia_synthesize_levels_nbhd')
+        elif sim is None and not sim_k:
             check(lib().ia_synthesize_levels(self._h, arr, len(args), ctypes.byref(st)), 'ia_synthesize_levels')
         else:
             check(lib().ia_synthesize_levels_kcoh(self._h, arr, len(args), None if sim is None else ctypes.c_void_p(int(sim)),
@@ -600,6 +640,20 @@ def wavefront_step(h, w, t):
     """(r0, M): step t covers pixels (r, t - 3r) for r in r0 .. r0 + M - 1."""
     r0, m = ctypes.c_int(), ctypes.c_int()
     check(lib().ia_wavefront_step(h, w, t, ctypes.byref(r0), ctypes.byref(m)), 'ia_wavefront_step')
+    return r0.value, m.value
+
+
+def wavefront_shape_pad(h, w, pad):
+    """(steps, max_queries) of the schedule t = col + (pad + 1) row (include/ia.h ia_wavefront_shape_pad)"""
+    s, m = ctypes.c_int64(), ctypes.c_int64()
+    check(lib().ia_wavefront_shape_pad(h, w, pad, ctypes.byref(s), ctypes.byref(m)), 'ia_wavefront_shape_pad')
+    return s.value, m.value
+
+
+def wavefront_step_pad(h, w, pad, t):
+    """(r0, M): step t covers pixels (r, t - (pad + 1) r) for r in r0 .. r0 + M - 1."""
+    r0, m = ctypes.c_int(), ctypes.c_int()
+    check(lib().ia_wavefront_step_pad(h, w, pad, t, ctypes.byref(r0), ctypes.byref(m)), 'ia_wavefront_step_pad')
     return r0.value, m.value
 
 

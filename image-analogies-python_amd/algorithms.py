@@ -200,6 +200,8 @@ def build_similarity(A_pyr, Ap_pyr_list, c, ctx=None):
     sims = {}
     if K <= 0:
         return sims
+    from .image_analogies import require_default_windows
+    require_default_windows(c, 'build_similarity')
     if K > _native.KCOH_MAX:
         raise ValueError('kcoh_k must be 0..%d (got %d)' % (_native.KCOH_MAX, K))
     L = c.max_levels if getattr(c, 'max_levels', None) else len(Ap_pyr_list[0])

@@ -22,6 +22,19 @@ n_half = (n_lg * n_lg) // 2   # fine scale half neighborhood size (config.py:18,
 pad_sm = n_sm // 2            # config.py:19
 pad_lg = n_lg // 2            # config.py:20
 
+
+
+def set_windows(sm, lg):
+    """Set the neighbourhood sizes and what the reference derives from them at import (config.py:18-20):
+    n_sm, n_lg, n_half, pad_sm, pad_lg together.  Setting n_lg alone leaves the other three stale, which
+    image_analogies.level_windows refuses."""
+    global n_sm, n_lg, n_half, pad_sm, pad_lg
+    n_sm, n_lg = int(sm), int(lg)
+    n_half = (n_lg * n_lg) // 2
+    pad_sm = n_sm // 2
+    pad_lg = n_lg // 2
+
+
 # runtime slots filled by setup_vars / img_setup (config.py:22-26)
 num_ch = None
 max_levels = None
@@ -37,6 +50,8 @@ device = None        # HIP device ordinal (None: LOCAL_RANK or 0)
 gpu_preprocess = True  # Gaussian pyramids + YIQ matrices on the GPU (bit-identical to the host code)
 kcoh_k = 0           # K > 0 (<= 15): k-coherence search with K similar rows per DB row: no
                      # DB scan, NOT the reference's result; 0 = the exact path
+# n_sm / n_lg other than 3 / 5 (set_windows): n_sm in {1, 3, 5}, n_lg in {3, 5, 7, 9}, feature width <= 167; those levels
+# run through ia_synthesize_levels_nbhd: exact, unpruned, without debug records or kcoh_k
 kcoh_min_rows = 1024  # levels with fewer DB rows stay exact when kcoh_k > 0
 
 

@@ -54,7 +54,7 @@ using namespace ia_host;
 extern "C" {
 
 const char *ia_last_error(void) { return g_last_error.c_str(); }
-int ia_version(void) { return 3; }
+int ia_version(void) { return 4; }
 
 int ia_init(int device, ia_ctx **out) {
   if (!out) return fail(IA_EINVAL, "ia_init: out is NULL");

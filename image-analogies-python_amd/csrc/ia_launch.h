@@ -1,6 +1,6 @@
 // ia_launch.h — host launchers of the kernels in ia_level_db.hip, ia_gather.hip, ia_k3.hip,
 // ia_kernels.hip (the per-step merges), ia_merge_shard.hip, ia_dense.hip, ia_k3r.hip, ia_prune.hip,
-// ia_kcoh.hip, ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
+// ia_kcoh.hip, ia_nbhd.hip, ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
 // ia_k3.hip and ia_k3r.hip scan with one body (ia_k3_scan.h): ia_launch_k3, ia_launch_k3r_count and
 // ia_launch_k3r_fill take the same geometry (n_tiles, tpw, nwg; qt <= ia_k3_qtmax(KH) tiles from qt0).
 #pragma once
@@ -127,6 +127,29 @@ int ia_kcoh_scan_waves(int64_t NA);
 void ia_launch_kcoh_step(const LevelGeo &g, const StepDesc &sd, const Imgs &A, const Imgs &B, const JobSet &jobs,
                          const double *db64, const int32_t *sim, int K, int H, void *part, unsigned *cnt, hipStream_t st);
 void ia_launch_kcoh_check(const int32_t *sim, int64_t n, int NA, unsigned *err, hipStream_t st);
+// exact levels for runtime window sizes (ia_nbhd.hip; include/ia.h ia_synthesize_levels_nbhd): the
+// windows of a level and where a row's four parts start (o1, o2, o3; D values in all)
+struct NbhdGeo {
+  int ch, n_sm, n_lg, p_s, p_l, n_half;
+  int o1, o2, o3, D;
+};
+inline NbhdGeo ia_nbhd_geo(int ch, int n_sm, int n_lg) {
+  NbhdGeo w{ch, n_sm, n_lg, n_sm / 2, n_lg / 2, n_lg * n_lg / 2, 0, 0, 0, 0};
+  w.o1 = ch * n_sm * n_sm;
+  w.o2 = w.o1 + ch * n_lg * n_lg;
+  w.o3 = w.o2 + ch * n_sm * n_sm;
+  w.D = w.o3 + ch * w.n_half;
+  return w;
+}
+// the fp64 row DB (NA x w.D, contiguous), then mu[0..D) = its column means and *amax_bits (zeroed by
+// the caller) = the bits of the largest centred |value| as a float, rounded up
+void ia_launch_nbhd_rows(const NbhdGeo &w, const Imgs &A, const APairs &ap, int64_t NA, double *rows, double *mu,
+                         unsigned *amax_bits, hipStream_t st);
+// the step's query rows q[m, 0..D), m < sd.J sd.M (pixel (r, sd.t - (p_l + 1) r)), and its pixels'
+// coherence pick, kappa rule and writeback from the certified winners idx[m]
+void ia_launch_nbhd_gather(const NbhdGeo &w, const StepDesc &sd, const Imgs &B, const JobSet &jobs, double *q, hipStream_t st);
+void ia_launch_nbhd_finish(const NbhdGeo &w, const LevelGeo &g, const StepDesc &sd, const Imgs &A, const JobSet &jobs,
+                           const double *rows, const double *q, const int64_t *idx, hipStream_t st);
 // GPU preprocessing (ia_pyramid.hip)
 void ia_launch_pyramid_reduce(const double *in, double *out, double *tmp, double *sm, double *mm, int h, int w, int ch,
                               const double *w7, hipStream_t st);

@@ -1,7 +1,8 @@
 // ia_level.h — what the phases of a level call (ia_synthesize_levels) hand to each other: the
 // plan, the staged inputs, a step's descriptor, the stamp slots, the scan tally and the link
 // between pipelined levels, and the phase functions that ia_level_plan.cpp, ia_level_stats.cpp
-// and ia_level_kcoh.cpp define for the level call in ia_level_run.cpp (its steps: ia_level_run.h).
+// and ia_level_kcoh.cpp define for the level call in ia_level_run.cpp (its steps: ia_level_run.h), and
+// what ia_level_nbhd.cpp's call (other window sizes) takes from them.
 #pragma once
 #include <chrono>
 #include <thread>
@@ -232,6 +233,7 @@ struct ScanTally {
 
 // phases 1-3 (ia_level_plan.cpp), in the order ia_synthesize_levels calls them
 int check_level_args(const ia_level_args *a);
+int check_level_batch(const ia_level_args *args, int n_jobs);
 int plan_shards(ia_ctx *c, const ia_level_args *args, int J, LevelPlan &P);
 int stage_level(ia_ctx *c, const ia_level_args *args, const LevelPlan &P, LevelInputs &in);
 int probe_matcher(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, bool *use_h);
@@ -254,5 +256,10 @@ int finish_level(ia_ctx *c, const ia_level_args *args, const LevelPlan &P, const
 int check_kcoh(ia_ctx *c, const ia_level_args *args, int J, const int32_t *sim, int sim_k);
 int run_kcoh_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const int32_t *sim_in, int K,
                    ia_stats *stats);
+
+// levels of other window sizes (ia_level_nbhd.cpp): what the sizes, the context and
+// the batch must be for one, and the level after plan_shards and stage_level (P.g.D = w.D)
+int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg);
+int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const NbhdGeo &w, ia_stats *stats);
 
 }  // namespace ia_host

@@ -1,0 +1,184 @@
+// ia_level_nbhd.cpp — exact levels for window sizes other than 3x3 / 5x5 (ia_synthesize_levels_nbhd,
+// DESIGN.md §11): the call, its checks, its step loop and the wavefront's shape for any skew.  It
+// shares the plan's first half, the staging and finish_level with the default path
+// (ia_level_run.cpp) and none of its steps: a step here is the window kernels of ia_nbhd.hip around
+// the index's query prep, fp32 scan and certified merge (ia_dense.hip, ia_k3.hip).
+#include <cmath>
+#include <cstring>
+
+#include "ia_level.h"
+
+namespace ia_host {
+
+int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg) {
+  const bool dep = c->dep != nullptr;
+  c->dep = nullptr;  // one level call per ia_pipeline_depend, refused or not
+  c->dep_gen = 0;
+  const int ch = args[0].ch;
+  const NbhdGeo w = ia_nbhd_geo(ch, n_sm, n_lg);
+  const bool sizes = (n_sm == 1 || n_sm == 3 || n_sm == 5) && (n_lg == 3 || n_lg == 5 || n_lg == 7 || n_lg == 9);
+  if (!sizes || w.D > IA_MAX_D - 1)
+    return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: n_sm = " + std::to_string(n_sm) + ", n_lg = " + std::to_string(n_lg) +
+                               " at " + std::to_string(ch) + " channel(s)" +
+                               (sizes ? " gives D = " + std::to_string(w.D) + " features" : std::string()) +
+                               ": n_sm must be 1, 3 or 5, n_lg 3, 5, 7 or 9, and D = ch (2 n_sm^2 + n_lg^2 + n_lg^2 / 2) <= " +
+                               std::to_string(IA_MAX_D - 1));
+  if (c->world > 1 || c->shard_emulate > 1)
+    return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: does not run on a sharded or shard-emulating context");
+  if (c->p_record || dep) return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: levels of this call are not pipelined");
+  for (int j = 0; j < J; j++)
+    if (args[j].dbg_src) return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: produces no debug records");
+  return IA_OK;
+}
+
+// the level's ia_stats: the pixel counters from the stats words (k_nbhd_finish sets the coherence and
+// kappa bits), the scan launches, and the level's two event brackets
+static int accumulate_nbhd_stats(ia_ctx *c, const LevelPlan &P, int64_t scans, ia_stats *stats) {
+  unsigned long long ctr[5];
+  HIP_TRY(hipMemcpy(ctr, c->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));
+  float ms_db = 0.f, ms_syn = 0.f;
+  hipEventElapsedTime(&ms_db, c->lv0, c->lv1);
+  hipEventElapsedTime(&ms_syn, c->lv1, c->lv2);
+  stats->pixels += P.NB * P.J;
+  stats->steps += P.T;
+  stats->nbhd_levels += P.J;
+  stats->coherence_wins += (int64_t)ctr[2];
+  stats->kappa_ambiguous += (int64_t)ctr[4];
+  stats->dist_launches += scans;
+  stats->db_ms += ms_db;
+  stats->synth_ms += ms_syn;
+  return IA_OK;
+}
+
+// The level after its staging.  DB: the fp64 rows with their column statistics (one read-back: it
+// also finds a non-finite A side before any step runs), then the index's centred, prescaled fp32
+// tiles.  Step t, all jobs: gather the query rows, the index's query prep, its scan in blocks of
+// ia_k3_qtmax(KH) query tiles, its certified merge, then coherence / kappa / writeback: five
+// launches (more scans when the step is wider than one block), nothing fused, nothing pruned.
+int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const NbhdGeo &w, ia_stats *stats) {
+  const LevelGeo &g = P.g;
+  const int D = w.D, KH = g.KH;
+  int rc;
+  ia_wavefront_shape_pad(g.bh, g.bw, w.p_l, &P.T, &P.Mmax);
+  P.Mtmax = P.Mmax * P.J;
+  P.Mpad_max = tile_pad(P.Mtmax);
+  // the index's geometry rule (ia_index_build)
+  const int tpw = std::max(4, (g.n_tiles + IA_WG_TARGET - 1) / IA_WG_TARGET), nwg = (g.n_tiles + tpw - 1) / tpw;
+  if ((rc = stage_jobs(c, P, in)) || (rc = c->db64.ensure((size_t)g.NA * D * 8)) || (rc = c->mu.ensure((size_t)D * 8)) ||
+      (rc = c->absmax.ensure(4)) || (rc = c->Rbits.ensure(4)) || (rc = c->counters.ensure(5 * 8)) ||
+      (rc = c->db.ensure((size_t)g.n_tiles * IA_TILE * 2 * KH * 4)) || (rc = c->q64.ensure((size_t)P.Mtmax * D * 8)) ||
+      (rc = c->qn2.ensure((size_t)P.Mpad_max * 8)) || (rc = c->qf.ensure((size_t)P.Mpad_max * 2 * KH * 4)) ||
+      (rc = c->rec.ensure((size_t)P.Mtmax * nwg * 16)) || (rc = c->recT.ensure((size_t)P.Mtmax * nwg * 4)) ||
+      (rc = c->win.ensure((size_t)P.Mtmax * 8)) || (rc = c->allwin.ensure((size_t)P.Mtmax * 8)))
+    return rc;
+  double *rows = c->db64.as<double>(), *mu = c->mu.as<double>(), *q64 = c->q64.as<double>();
+  int64_t *idx = c->win.as<int64_t>();
+  HIP_TRY(hipMemsetAsync(c->absmax.p, 0, 4, c->st));
+  HIP_TRY(hipMemsetAsync(c->Rbits.p, 0, 4, c->st));
+  HIP_TRY(hipMemsetAsync(c->counters.p, 0, 5 * 8, c->st));
+  HIP_TRY(hipEventRecord(c->lv0, c->st));
+  ia_launch_nbhd_rows(w, in.Aim, in.Apairs, g.NA, rows, mu, c->absmax.as<unsigned>(), c->st);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> mu_h(D);
+  unsigned abits = 0;
+  HIP_TRY(hipMemcpyAsync(mu_h.data(), mu, (size_t)D * 8, hipMemcpyDeviceToHost, c->st));
+  HIP_TRY(hipMemcpyAsync(&abits, c->absmax.p, 4, hipMemcpyDeviceToHost, c->st));
+  HIP_TRY(hipStreamSynchronize(c->st));
+  float amaxf;
+  std::memcpy(&amaxf, &abits, 4);
+  bool finite = std::isfinite(amaxf);
+  for (int f = 0; f < D; f++) finite = finite && std::isfinite(mu_h[f]);
+  if (!finite) return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: the A side must be finite (and its column sums too)");
+  // prescale as ia_index_build's: the largest centred |value| lands in [0.5, 1) (an all-equal DB keeps 1)
+  const double amax = amaxf;
+  const double sc = amax > 0. ? std::ldexp(1.0, -std::max(-500, std::min(500, std::ilogb(amax) + 1))) : 1.;
+  ia_launch_dense_db(KH, rows, g.NA, D, g.n_tiles, mu, sc, c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
+  HIP_TRY(hipEventRecord(c->lv1, c->st));
+
+  MergeArgs ma;
+  ma.db64 = nullptr;
+  ma.rec = c->rec.as<float4>();
+  ma.recT = c->recT.as<float>();
+  ma.q64 = nullptr;
+  ma.qn2 = c->qn2.as<double>();
+  ma.Rbits = c->Rbits.as<unsigned>();
+  ma.nwg = nwg;
+  ma.tpw = tpw;
+  ma.pos0 = 0;
+  ma.pos_end = g.n_tiles * IA_TILE;
+  ma.NT = g.n_tiles;
+  ma.NA = (int)g.NA;
+  ma.pos2row = nullptr;
+  ma.rr = 0;
+  ma.qinfo = nullptr;
+  ma.boxes = nullptr;
+  ma.ufac = 0.;
+  ma.img_rows = 0;
+  ma.eps_c = ia_eps_c(2 * KH);
+  ma.eps_a = 0.;
+  const int qtmax = ia_k3_qtmax(KH);
+  int64_t scans = 0;
+  for (int64_t t = 0; t < P.T; t++) {
+    StepDesc sd{(int)t, 0, 0, 0, P.J};
+    ia_wavefront_step_pad(g.bh, g.bw, w.p_l, t, &sd.r0, &sd.M);
+    if (sd.M <= 0) continue;  // levels narrower than p_l + 1 columns have empty steps
+    const int Mt = P.J * sd.M;
+    sd.Mpad = (int)tile_pad(Mt);
+    ia_launch_nbhd_gather(w, sd, in.Bim, in.jobs(), q64, c->st);
+    ia_launch_dense_query(KH, q64, Mt, D, sd.Mpad, mu, sc, c->qn2.as<double>(), c->qf.as<float>(), c->st);
+    const int qtt = sd.Mpad / IA_TILE;
+    for (int qt0 = 0; qt0 < qtt; qt0 += qtmax, scans++)  // (index_scan_tiles' blocking)
+      ia_launch_k3(KH, std::min(qtmax, qtt - qt0), c->db.as<float4>(), c->qf.as<float4>(), g.n_tiles, tpw, qt0, Mt, nwg, 0,
+                   g.n_tiles, c->rec.as<float4>(), c->recT.as<float>(), c->st);
+    ia_launch_merge_dense(ma, rows, D, q64, Mt, sc * sc, idx, c->allwin.as<double>(), c->st);
+    ia_launch_nbhd_finish(w, g, sd, in.Aim, in.jobs(), rows, q64, idx, c->st);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->lv2, c->st));
+  if ((rc = finish_level(c, args, P, in, false, stats != nullptr))) return rc;
+  return stats ? accumulate_nbhd_stats(c, P, scans, stats) : IA_OK;
+}
+
+}  // namespace ia_host
+
+using namespace ia_host;
+
+extern "C" {
+
+int ia_wavefront_shape_pad(int h, int w, int pad, int64_t *steps, int64_t *max_queries) {
+  if (h < 1 || w < 1 || pad < 0 || pad > 4) return fail(IA_EINVAL, "ia_wavefront_shape_pad: empty level or pad outside 0..4");
+  const int64_t k = pad + 1;
+  if (steps) *steps = (int64_t)w + k * (int64_t)(h - 1);
+  if (max_queries) *max_queries = std::min<int64_t>(h, (w + k - 1) / k);
+  return IA_OK;
+}
+
+int ia_wavefront_step_pad(int h, int w, int pad, int64_t t, int *r0, int *M) {
+  const int64_t k = pad + 1;
+  if (h < 1 || w < 1 || pad < 0 || pad > 4 || !r0 || !M || t < 0 || t >= (int64_t)w + k * (int64_t)(h - 1))
+    return fail(IA_EINVAL, "ia_wavefront_step_pad: bad step");
+  const int64_t over = t - w + 1;  // rows r with t - k r >= w lie before the step
+  const int64_t r_lo = over <= 0 ? 0 : (over + k - 1) / k;
+  const int64_t r_hi = std::min<int64_t>(h - 1, t / k);
+  *r0 = (int)r_lo;
+  *M = (int)(r_hi - r_lo + 1);
+  return IA_OK;
+}
+
+int ia_synthesize_levels_nbhd(ia_ctx *c, const ia_level_args *args, int n_jobs, int n_sm, int n_lg, ia_stats *stats) {
+  if (!c || !args) return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: NULL argument");
+  int rc;
+  if ((rc = check_level_batch(args, n_jobs)) || (rc = check_nbhd(c, args, n_jobs, n_sm, n_lg))) return rc;
+  HIP_TRY(hipSetDevice(c->dev));
+  const NbhdGeo w = ia_nbhd_geo(args[0].ch, n_sm, n_lg);
+  LevelPlan P;
+  LevelInputs in;
+  if ((rc = plan_shards(c, args, n_jobs, P))) return rc;
+  P.g.D = w.D;  // this call's weight length and row width (plan_shards set the 3 / 5 ones)
+  P.g.KH = kh_for(w.D + 1);
+  P.DP = 2 * P.g.KH;
+  if ((rc = stage_level(c, args, P, in))) return rc;
+  return run_nbhd_level(c, args, P, in, w, stats);
+}
+
+}  // extern "C"

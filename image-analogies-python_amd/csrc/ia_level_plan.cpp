@@ -141,6 +141,24 @@ int check_level_args(const ia_level_args *a) {
   return IA_OK;
 }
 
+// the jobs of one level call: each valid, all on one A side with one set of shapes
+int check_level_batch(const ia_level_args *args, int n_jobs) {
+  if (n_jobs < 1 || n_jobs > IA_MAX_JOBS)
+    return fail(IA_EINVAL, "ia_synthesize_levels: n_jobs must be 1.." + std::to_string(IA_MAX_JOBS));
+  const ia_level_args *a = &args[0];
+  int rc;
+  for (int j = 0; j < n_jobs; j++) {
+    const ia_level_args *x = &args[j];
+    if ((rc = check_level_args(x))) return rc;
+    if (x->ch != a->ch || x->n_ap != a->n_ap || x->n_a != a->n_a || x->a_h != a->a_h || x->a_w != a->a_w || x->b_h != a->b_h ||
+        x->b_w != a->b_w || x->mem != a->mem)
+      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch has the same shapes, channels, n_a and mem kind");
+    if (x->A != a->A || x->Ac != a->Ac || x->Ap != a->Ap || x->Apc != a->Apc)
+      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch shares the A side (same A / A' buffers)");
+  }
+  return IA_OK;
+}
+
 int plan_shards(ia_ctx *c, const ia_level_args *args, int J, LevelPlan &P) {
   const ia_level_args *a = &args[0];
   int rc;

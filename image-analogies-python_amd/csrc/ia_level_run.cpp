@@ -402,19 +402,8 @@ int ia_synthesize_levels(ia_ctx *c, const ia_level_args *args, int n_jobs, ia_st
 // the level call: the exact path (sim_k = 0) or k-coherence search on the similarity sets sim
 int ia_synthesize_levels_kcoh(ia_ctx *c, const ia_level_args *args, int n_jobs, const int32_t *sim, int sim_k, ia_stats *stats) {
   if (!c || !args) return fail(IA_EINVAL, "ia_synthesize_level: NULL argument");
-  if (n_jobs < 1 || n_jobs > IA_MAX_JOBS)
-    return fail(IA_EINVAL, "ia_synthesize_levels: n_jobs must be 1.." + std::to_string(IA_MAX_JOBS));
-  const ia_level_args *a = &args[0];
   int rc;
-  for (int j = 0; j < n_jobs; j++) {
-    const ia_level_args *x = &args[j];
-    if ((rc = check_level_args(x))) return rc;
-    if (x->ch != a->ch || x->n_ap != a->n_ap || x->n_a != a->n_a || x->a_h != a->a_h || x->a_w != a->a_w || x->b_h != a->b_h ||
-        x->b_w != a->b_w || x->mem != a->mem)
-      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch has the same shapes, channels, n_a and mem kind");
-    if (x->A != a->A || x->Ac != a->Ac || x->Ap != a->Ap || x->Apc != a->Apc)
-      return fail(IA_EINVAL, "ia_synthesize_levels: every job of a batch shares the A side (same A / A' buffers)");
-  }
+  if ((rc = check_level_batch(args, n_jobs))) return rc;
   if ((rc = check_kcoh(c, args, n_jobs, sim, sim_k))) return rc;
   HIP_TRY(hipSetDevice(c->dev));
 

@@ -42,7 +42,8 @@ def img_setup(A_fname, Ap_fname_list, B_fname, out_path, c):
     (A_i, A'_i), every image of one shape.  Each A_i is then scaled, converted, compressed and
     reduced on its own, remap_lum remaps each pair (A_i, A'_i) with A_i's own mean and deviation,
     and the first return value is the list of the A_i's pyramids."""
-    check_windows(c)
+    if level_windows(c, ch=1) == (3, 5):   # (the channel count is known below: checked again there)
+        check_windows(c)
     os.makedirs(out_path, exist_ok=True)
     pairs = isinstance(A_fname, (list, tuple))
     if pairs and len(A_fname) != len(Ap_fname_list):
@@ -82,6 +83,7 @@ def img_setup(A_fname, Ap_fname_list, B_fname, out_path, c):
     compressed = [compress_values(a, B, c.AB_weight) for a in A_list]   # (ratio A_i, ratio B) each
     A_list, B = [x[0] for x in compressed], compressed[0][1]
     c.num_ch, c.padding_sm, c.padding_lg, c.weights = setup_vars(A_list[0])
+    level_windows(c)
 
     A_pyr_list = [compute_gaussian_pyramid(a, c.n_sm, c.n_levels, gpu) for a in A_list]
     A_pyr = A_pyr_list[0]
@@ -119,6 +121,37 @@ def check_windows(c):
                          'got n_sm = %r, n_lg = %r, n_half = %r)' % (n_sm, n_lg, getattr(c, 'n_half', None)))
 
 
+def level_windows(c, ch=None):
+    """The validated (n_sm, n_lg) of c for images of ch channels (None: c.num_ch, or 1 before img_setup set it).  (3, 5) is the default level call; every other supported pair
+    runs through ia_synthesize_levels_nbhd.  ValueError when n_half / pad_sm /
+    pad_lg do not follow from the sizes (the reference derives them at import: use
+    config.set_windows), and for sizes the library does not take."""
+    n_sm, n_lg = getattr(c, 'n_sm', 3), getattr(c, 'n_lg', 5)
+    ch = ch or getattr(c, 'num_ch', None) or 1
+    ok = n_sm in _native.NBHD_N_SM and n_lg in _native.NBHD_N_LG
+    if ok:
+        derived = ((n_lg * n_lg) // 2, n_sm // 2, n_lg // 2)
+        have = tuple(getattr(c, k, d) for k, d in zip(('n_half', 'pad_sm', 'pad_lg'), derived))
+        if tuple(int(x) for x in have) != derived or any(int(x) != x for x in have):
+            raise ValueError('n_half, pad_sm, pad_lg = %r do not follow from n_sm = %r, n_lg = %r (%r expected): set the '
+                             'sizes with config.set_windows(n_sm, n_lg), which sets all five' % (have, n_sm, n_lg, derived))
+    if not ok or _native.feature_width(n_sm, n_lg, ch) > _native.NBHD_MAX_D:
+        raise ValueError('supported window sizes are n_sm in %r, n_lg in %r with ch (2 n_sm^2 + n_lg^2 + n_lg^2 // 2) <= %d '
+                         'features (got n_sm = %r, n_lg = %r at %d channel(s)%s)'
+                         % (_native.NBHD_N_SM, _native.NBHD_N_LG, _native.NBHD_MAX_D, n_sm, n_lg, ch,
+                            ': %d features' % _native.feature_width(n_sm, n_lg, ch) if ok else ''))
+    return int(n_sm), int(n_lg)
+
+
+def require_default_windows(c, what):
+    """The paths written for 3 / 5 windows only (debug records, k-coherence search, sweeps, level
+    pipelining) refuse other sizes at once."""
+    win = level_windows(c, ch=1)
+    if win != (3, 5):
+        raise ValueError('%s runs with n_sm = 3, n_lg = 5 only (got %r): other window sizes take the plain exact '
+                         'level call' % (what, win))
+
+
 def synthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, c, ctx=None, stats=None, on_level=None, debug=None, sim=None):
     """The level loop of image_analogies_main (image_analogies.py:130-239) on the GPU.
     Bp_pyr levels 1..max_levels-1 are synthesised in place; returns ({level: s}, {level: im}).
@@ -130,8 +163,20 @@ def synthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, c, ctx=None, stats=Non
     sim: {level: similarity sets} (algorithms.build_similarity): those levels run by k-coherence
     search, the others exactly; None: computed here when c.kcoh_k > 0 (for the levels with at least
     c.kcoh_min_rows DB rows), else every level is exact.  A k-coherence level is not the reference's
-    result and takes no debug records."""
-    check_windows(c)
+    result and takes no debug records.
+    c.n_sm / c.n_lg other than 3 / 5 (level_windows): every level runs through ia_synthesize_levels_nbhd,
+    with c.weights of that width; debug, sim and c.kcoh_k > 0 are refused."""
+    lv = Ap_pyr_list[0][-1]
+    windows = level_windows(c, ch=1 if lv.ndim == 2 else lv.shape[2])
+    if windows == (3, 5):
+        check_windows(c)
+        windows = None
+    else:
+        if debug is not None:
+            require_default_windows(c, 'debug=')
+        if sim or getattr(c, 'kcoh_k', 0):
+            require_default_windows(c, 'k-coherence search (kcoh_k > 0 / sim)')
+        sim = {}
     ctx = ctx or default_context()
     L = c.max_levels
     if sim is None:
@@ -149,7 +194,7 @@ def synthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, c, ctx=None, stats=Non
             a_levels(A_pyr, level), a_levels(A_pyr, level - 1), [p[level] for p in Ap_pyr_list],
             [p[level - 1] for p in Ap_pyr_list],
             B_pyr[level], B_pyr[level - 1], Bp_pyr[level - 1], Bp_pyr[level], c.weights, kf, stats, debug=dbg,
-            sim=sim.get(level))
+            sim=sim.get(level), windows=windows)
         if on_level is not None:
             on_level(level, S, IM)
     if stats.kappa_ambiguous > amb0:

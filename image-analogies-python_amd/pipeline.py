@@ -18,7 +18,9 @@ def run_levels_pipelined(level_fn, ctxs, L, stats):
     (ia_pipeline_depend with the generation the level-l call gets), level l + n follows level l
     on the same context.  The finest level runs on ctxs[0]; with n = 3 it starts as soon as the
     next-coarser level's first steps are done instead of after level L - 3 ends."""
-    from . import _native
+    from . import _native, config
+    from .image_analogies import require_default_windows
+    require_default_windows(config, 'level pipelining')   # (refused by the library too: a recording context)
     for c in ctxs:
         c.set_option('pipeline_record', 1)
     base = [c.pipeline_generation() for c in ctxs]

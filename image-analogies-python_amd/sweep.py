@@ -54,6 +54,8 @@ class Sweep(object):
         the reference's rule (image_analogies.py:82-86): the coarsest levels pair and the deeper
         pyramid's extra fine levels are dropped, with the reference's warning; 'fine' pairs the
         finest levels (B level k + d <-> A level k, cfg4's pairing)."""
+        from .image_analogies import require_default_windows
+        require_default_windows(_config, 'sweep.Sweep')
         min_size = _config.n_sm if min_size is None else min_size
         if level_align not in ('coarse', 'fine'):
             raise ValueError("level_align must be 'coarse' or 'fine'")

@@ -118,6 +118,9 @@ typedef struct {
   int64_t kcoh_fallbacks;   /* their pixels without a base row: exact NN over the whole DB */
   int64_t kcoh_candidates;  /* candidate rows (base rows and their similar rows) whose exact
                              * distance was computed; a fallback pixel's DB scan is not counted */
+  /* levels of other window sizes (ia_synthesize_levels_nbhd) */
+  int64_t nbhd_levels;      /* levels (jobs) run by that call; it also adds to pixels, steps,
+                             * coherence_wins, kappa_ambiguous, dist_launches, db_ms and synth_ms */
 } ia_stats;
 
 /* One pyramid level (image_analogies.py:130-239).  Shapes: A/A' level l is (a_h, a_w[, ch]),
@@ -166,7 +169,8 @@ typedef struct {
 int ia_init(int device, ia_ctx **out);
 void ia_destroy(ia_ctx *ctx);
 const char *ia_last_error(void);
-int ia_version(void);  /* 3: ia_synthesize_levels_kcoh, ia_index_similarity, ia_stats.kcoh_*; 2: ia_level_args.n_a
+int ia_version(void);  /* 4: ia_synthesize_levels_nbhd, ia_wavefront_*_pad, ia_stats.nbhd_levels;
+                        * 3: ia_synthesize_levels_kcoh, ia_index_similarity, ia_stats.kcoh_*; 2: ia_level_args.n_a
                         * (1: the struct ended at dbg_dist) */
 /* Options: "time_dist" = S (0 = off): bracket the MFMA distance launches of every S-th
  * wavefront step with HIP events; ia_stats.dist_ms / dist_flops_timed then give the kernel's
@@ -317,6 +321,36 @@ int ia_synthesize_levels(ia_ctx *ctx, const ia_level_args *args, int n_jobs, ia_
 int ia_synthesize_levels_kcoh(ia_ctx *ctx, const ia_level_args *args, int n_jobs, const int32_t *sim, int sim_k,
                               ia_stats *stats);
 
+/* The exact level for other window sizes: n_sm x n_sm coarse and n_lg x n_lg fine
+ * neighbourhoods (config.py:15-16) given at run time.  With p_s = n_sm / 2, p_l = n_lg / 2, n_half =
+ * n_lg^2 / 2 (integer divisions) and D = ch (2 n_sm^2 + n_lg^2 + n_half):
+ *   DB row of pixel (r, c) of pair i = [A_i n_sm x n_sm at (r / 2, c / 2) of level l-1 | A_i n_lg x n_lg
+ *     at (r, c) | A'_i n_sm x n_sm | A'_i first n_half cells of its n_lg x n_lg], each window row-major
+ *     and channel-minor with symmetric padding (periodic where the image is smaller than the pad):
+ *     compute_feature_array's row (algorithms.py:11-47); the query row likewise from B, B';
+ *   NN = the smallest fp64 squared L2 in numpy's pairwise order, lowest row on ties;
+ *   coherence = rows r - p_l .. r, columns c - p_l .. c + p_l in product order, raster-earlier cells
+ *     whose shifted source lies inside A, ranked by the correctly rounded sqrt of the pairwise sum,
+ *     first argmin (ia_coherence_batch's rule with pad = p_l);
+ *   kappa rule = compute_distance with args[j].weights, which holds D values
+ *     (config.compute_weights(n_sm, n_lg, n_half, ch)): x.dot(x) in the BLAS order of dbg_dist, the
+ *     correctly rounded sqrt, y * y, and the kappa_ambiguous audit, as the default call does them;
+ *   schedule t = col + (p_l + 1) row: every B' pixel a pixel reads in its causal half window or
+ *     its coherence cells was written at an earlier step if raster-earlier and is written at a later
+ *     step if raster-later (it still holds the initial B'), under reflection at every border.
+ * Supported: n_sm in {1, 3, 5}, n_lg in {3, 5, 7, 9} (one coherence cell per lane: p_l <= 4), ch 1..3
+ * and D <= 167 (the fp32 scan's widest instance).  (3, 5) is accepted and equals
+ * ia_synthesize_levels bit for bit.  Batching (1 <= n_jobs <= 32), n_a and both mem kinds as there.
+ * Image values need only be finite: the scan runs on a centred, prescaled fp32 copy, as the
+ * index's does, so there is no +-64 gate.  The step is not fused, pruned or split-f16: gather,
+ * query prep, fp32 scan over the whole DB, certified merge, finish.
+ * IA_EINVAL before any step runs and with nothing written: unsupported sizes (checked before any
+ * GPU call; the message names the sizes and D), debug buffers, a context that is a rank of a
+ * shard or emulates one, a context with "pipeline_record" = 1 or a pending ia_pipeline_depend
+ * (which the refused call consumes), a non-finite value on the A side. */
+int ia_synthesize_levels_nbhd(ia_ctx *ctx, const ia_level_args *args, int n_jobs, int n_sm, int n_lg,
+                              ia_stats *stats);
+
 /* Level pipelining: level l + 1 of a job only reads B' of level l near
  * (r / 2, c / 2), so its wavefront step t needs level l's steps <= t / 2 + 4, not the whole level.
  * Two contexts driven from two host threads run alternate levels concurrently: the context of
@@ -450,6 +484,12 @@ int ia_chain_choice(int level_waves, int in_flight, int budget, int two_wave);
 int ia_wavefront_shape(int h, int w, int64_t *steps, int64_t *max_queries);
 /* Pixels of step t: rows r0 .. r0+M-1, pixel (r, t - 3r).  Used by the level driver. */
 int ia_wavefront_step(int h, int w, int64_t t, int *r0, int *M);
+/* The same two for the schedule t = col + (pad + 1) row of ia_synthesize_levels_nbhd (pad = n_lg / 2,
+ * 0..4): steps = w + (pad + 1)(h - 1), max_queries = min(h, ceil(w / (pad + 1))); step t holds the
+ * pixels (r, t - (pad + 1) r), r0 <= r < r0 + M (M = 0: none, on levels narrower than pad + 1).
+ * pad = 2 gives what ia_wavefront_shape / ia_wavefront_step give. */
+int ia_wavefront_shape_pad(int h, int w, int pad, int64_t *steps, int64_t *max_queries);
+int ia_wavefront_step_pad(int h, int w, int pad, int64_t t, int *r0, int *M);
 /* DB tiles [tile0, tile1) owned by `rank` of `world` for a level of n_rows DB rows.  The DB is
  * stored in NT = ceil(n_rows/32) tiles of 32 positions; position j of tile t holds row
  * j*NT + (t * (2654435761 mod NT) mod NT) (tile-strided and tile-scattered, so neighbouring A
