@@ -125,17 +125,31 @@ __device__ Winner certified_winner(const MergeArgs &a, int m, DistFn &&dist, uns
   return Winner{bd, bi};
 }
 
+// The rows a finish reads, as a policy R: row(i) where row i starts, dist(i, q) its exact unweighted
+// distance, len() the kappa dot's length (a constant or an int), pad() the window's p_l (Pad2 or an
+// int), ch() the channels.  LevelRows: a level's fp64 DB (K1b) under the default windows; the
+// window call brings its own (ia_nbhd.hip NbhdRows).
+template <int CH>
+struct LevelRows {
+  const double *__restrict__ db64;
+  __device__ __forceinline__ const double *row(int64_t i) const { return db64 + i * Geo<CH>::DS; }
+  __device__ __forceinline__ double dist(int64_t i, const double *q) const { return exact_dist_level<CH>(db64, i, q); }
+  __device__ __forceinline__ std::integral_constant<int, Geo<CH>::D> len() const { return {}; }
+  __device__ __forceinline__ Pad2 pad() const { return {}; }
+  __device__ __forceinline__ std::integral_constant<int, CH> ch() const { return {}; }
+};
+
 // best_coherence_match's pick for query pixel (r, c) (algorithms.py:92-130): candidates in
-// product(rows, cols) order, first argmin of the unweighted norm.  Independent of the NN winner,
-// so the exchange merge runs it while the peers' winners are in flight.
+// product(rows, cols) order (lane = window cell), first argmin of the correctly rounded sqrt of the
+// pairwise sum.  Independent of the NN winner, so the exchange merge runs it while the peers'
+// winners are in flight.  Every cell read is raster-earlier, hence of an earlier step.
 struct CohPick {
   int pr, pc, img;
   bool has;
 };
-template <int CH>
-__device__ __forceinline__ CohPick coherence_pick(const LevelGeo &g, const double *__restrict__ db64, int r, int c,
-                                                  const double *q, const int32_t *__restrict__ s,
-                                                  const int32_t *__restrict__ im) {
+template <class Rows>
+__device__ __forceinline__ CohPick coherence_pick(const Rows &R, const LevelGeo &g, int r, int c, const double *q,
+                                                  const int32_t *__restrict__ s, const int32_t *__restrict__ im) {
   const int lane = threadIdx.x & 63;
   const unsigned hw = (unsigned)g.ah * (unsigned)g.aw;
   const int qi = r * g.bw + c;
@@ -144,17 +158,15 @@ __device__ __forceinline__ CohPick coherence_pick(const LevelGeo &g, const doubl
   double dk = DBL_MAX;
   int64_t kk = INT64_MAX;
   int cpr = -1, cpc = -1, cim = 0;
-  if (lane < 15) {
-    const int nr = r - 2 + lane / 5, nc = c - 2 + lane % 5;
-    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < qi) {
-      const int nb = nr * g.bw + nc;
-      const int tr = s[2 * nb] + r - nr, tc = s[2 * nb + 1] + c - nc;
-      if (tr >= 0 && tr < g.ah && tc >= 0 && tc < g.aw) {
-        cim = im[nb];
-        cpr = tr;
-        cpc = tc;
-        const int64_t row = (int64_t)cim * hw + (int64_t)tr * g.aw + tc;
-        dk = cr_sqrt(exact_dist_level<CH>(db64, row, q));
+  if (lane < causal_cells(R.pad())) {
+    const auto n = causal_cell(R.pad(), g.bw, r, c, qi, lane);
+    if (n.ok) {
+      const ShiftedSrc t = shifted_src(g.ah, g.aw, s[2 * n.nb], s[2 * n.nb + 1], r, c, n.nr, n.nc);
+      if (t.ok) {
+        cim = im[n.nb];
+        cpr = t.tr;
+        cpc = t.tc;
+        dk = cr_sqrt(R.dist((int64_t)cim * hw + (int64_t)t.tr * g.aw + t.tc, q));
         kk = lane;
       }
     }
@@ -171,13 +183,12 @@ __device__ __forceinline__ CohPick coherence_pick(const LevelGeo &g, const doubl
 }
 // kappa rule + writeback for query pixel (r, c) whose NN row is app_ix and coherence pick ck
 // (image_analogies.py:182-220, algorithms.py:133-135)
-template <int CH>
-__device__ void finish_pick(const LevelGeo &g, const Imgs &A, const double *__restrict__ db64, int r, int c,
-                            int64_t app_ix, const CohPick &ck, const double *q, int32_t *__restrict__ s,
-                            int32_t *__restrict__ im, double *__restrict__ Bp, const double *__restrict__ weights, double kf,
-                            unsigned *pstat, unsigned stat, int32_t *__restrict__ nn = nullptr) {
-  constexpr int D = Geo<CH>::D;
-  const int lane = threadIdx.x & 63;
+template <class Rows>
+__device__ void finish_pick(const Rows &R, const LevelGeo &g, const Imgs &A, int r, int c, int64_t app_ix, const CohPick &ck,
+                            const double *q, int32_t *__restrict__ s, int32_t *__restrict__ im, double *__restrict__ Bp,
+                            const double *__restrict__ weights, double kf, unsigned *pstat, unsigned stat,
+                            int32_t *__restrict__ nn = nullptr) {
+  const int lane = threadIdx.x & 63, CH = R.ch();
   const unsigned hw = (unsigned)g.ah * (unsigned)g.aw;
   const int qi = r * g.bw + c;
   int img = (int)((unsigned)app_ix / hw);
@@ -185,18 +196,14 @@ __device__ void finish_pick(const LevelGeo &g, const Imgs &A, const double *__re
   int pr = (int)(rem / (unsigned)g.aw), pc = (int)(rem - (unsigned)pr * (unsigned)g.aw);
   bool coh_won = false, kamb = false;
   if (ck.has) {
-    // compute_distance(AAp_feat, BBp_feat, weights) = norm((a - q) * w)**2 for app and coh
-    double part = 0.;
+    // compute_distance's norm((a - q) * w) for app (lane 0) and coh (lane 1)
+    double y = 0.;
     if (lane < 2) {
       const int ii = lane == 0 ? img : ck.img, rr_ = lane == 0 ? pr : ck.pr, cc_ = lane == 0 ? pc : ck.pc;
-      const double *arow = db64 + ((int64_t)ii * hw + (int64_t)rr_ * g.aw + cc_) * Geo<CH>::DS;
-      part = blas_dot_sq<D>([&](int f) { return (arow[f] - q[f]) * weights[f]; });
-      part = cr_sqrt(part);
+      const double *arow = R.row((int64_t)ii * hw + (int64_t)rr_ * g.aw + cc_);
+      y = cr_sqrt(blas_dot_sq(R.len(), [&](int f) { return (arow[f] - q[f]) * weights[f]; }));
     }
-    const double y_app = __shfl(part, 0, 64), y_coh = __shfl(part, 1, 64);
-    const double d_app = y_app * y_app, d_coh = y_coh * y_coh;
-    kamb = kappa_ambiguous(y_app, d_app, y_coh, d_coh, kf);
-    if (d_coh <= d_app * kf) {
+    if (kappa_rule(__shfl(y, 0, 64), __shfl(y, 1, 64), kf, &kamb)) {
       img = ck.img;
       pr = ck.pr;
       pc = ck.pc;
@@ -213,14 +220,13 @@ __device__ void finish_pick(const LevelGeo &g, const Imgs &A, const double *__re
   }
 }
 // coherence + kappa + writeback for query pixel (r, c) whose NN row is app_ix
-template <int CH>
-__device__ void finish_pixel(const LevelGeo &g, const Imgs &A, const double *__restrict__ db64, int r, int c, int64_t app_ix,
-                             const double *q,
+template <class Rows>
+__device__ void finish_pixel(const Rows &R, const LevelGeo &g, const Imgs &A, int r, int c, int64_t app_ix, const double *q,
                              int32_t *__restrict__ s, int32_t *__restrict__ im, double *__restrict__ Bp,
                              const double *__restrict__ weights, double kf, unsigned *pstat, unsigned stat,
                              int32_t *__restrict__ nn = nullptr) {
-  const CohPick ck = coherence_pick<CH>(g, db64, r, c, q, s, im);
-  finish_pick<CH>(g, A, db64, r, c, app_ix, ck, q, s, im, Bp, weights, kf, pstat, stat, nn);
+  const CohPick ck = coherence_pick(R, g, r, c, q, s, im);
+  finish_pick(R, g, A, r, c, app_ix, ck, q, s, im, Bp, weights, kf, pstat, stat, nn);
 }
 
 // row of the lowest set candidate bit (bit 2j: record j's best, bit 2j+1: its runner-up)

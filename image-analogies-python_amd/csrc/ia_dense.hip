@@ -205,10 +205,11 @@ __global__ void __launch_bounds__(IA_WG) k_coherence_batch(const double *__restr
   const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
   const int lane = threadIdx.x & 63;
   if (m >= nq) return;
-  const int row = px[2 * m], col = px[2 * m + 1], wd = 2 * pad + 1;
-  const int rr = row - pad + lane / wd, rc = col - pad + lane % wd;
-  const int64_t here = (int64_t)row * bp_w + col, ri = (int64_t)rr * bp_w + rc;
-  bool ok = lane < (pad + 1) * wd && rr >= 0 && rc >= 0 && rc < bp_w && ri < here;
+  const int row = px[2 * m], col = px[2 * m + 1];
+  const auto cl = causal_cell(pad, bp_w, row, col, (int64_t)row * bp_w + col, lane);
+  const int rr = cl.nr, rc = cl.nc;
+  const int64_t ri = cl.nb;
+  bool ok = lane < causal_cells(pad) && cl.ok;
   int pr0 = 0, pr1 = 0, img = 0;
   int64_t dbrow = 0;
   unsigned e = 0;
@@ -217,11 +218,12 @@ __global__ void __launch_bounds__(IA_WG) k_coherence_batch(const double *__restr
     ok = false;
   }
   if (ok) {
-    pr0 = s[2 * ri] + row - rr;
-    pr1 = s[2 * ri + 1] + col - rc;
+    const ShiftedSrc t = shifted_src(a_h, a_w, s[2 * ri], s[2 * ri + 1], row, col, rr, rc);
+    pr0 = t.tr;
+    pr1 = t.tc;
     img = im[ri];
-    ok = pr0 >= 0 && pr0 < a_h && pr1 >= 0 && pr1 < a_w;
-    dbrow = ((int64_t)img * a_h + pr0) * a_w + pr1;
+    ok = t.ok;
+    dbrow = src_row<int64_t>(a_h, a_w, img, pr0, pr1);
     if (ok && (dbrow < 0 || dbrow >= n)) {
       e |= 2u;
       ok = false;

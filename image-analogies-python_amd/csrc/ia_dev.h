@@ -19,6 +19,15 @@
 //   ia_k3r.hip          the index's fixed-radius search: the same scan body (ia_k3_scan.h) with a
 //                       threshold epilogue (count and fill passes), exact verification, per-query
 //                       sort (ia_index_*_radius)
+//   ia_kcoh.hip         k-coherence levels: a step without a DB scan (ia_synthesize_levels_kcoh)
+//   ia_nbhd.hip         exact levels for run-time window sizes (ia_synthesize_levels_nbhd)
+//
+// The per-pixel window rule lives here, once, for all of them: win_feat (feature f of a pixel),
+// causal_cell / shifted_src / src_row (window cell -> neighbour -> shifted source -> DB row),
+// blas_dot_sq and kappa_rule; the geometry is a constant (Geo<CH>, Pad2) on the default path and a
+// run-time value (NbhdGeo, int) in ia_nbhd.hip and k_coherence_batch.  ia_internal.h has ia_qpix
+// (step query -> pixel, any skew), ia_certify.h the coherence pick and the kappa finish over a row
+// policy.
 //
 // Here: feature geometry and access, numpy's and OpenBLAS's summation orders, the wave
 // reductions, the exact row distances and the certification bounds; at the end the two host
@@ -60,6 +69,9 @@ struct Geo {
   static constexpr int KH = DP / 2;                 // k-steps of the 32x32x2 chain
   static constexpr int KP = KH / 4;                 // float4 pieces per lane
   static constexpr int DS = ((D + 7) / 8) * 8;      // fp64 row-major DB row stride (doubles)
+  // the windows and where a row's four parts start, under NbhdGeo's names (ia_launch.h): the
+  // window rule below takes either, this one folding to constants
+  static constexpr int ch = CH, n_sm = 3, n_lg = 5, p_s = 1, p_l = 2, o1 = 9 * CH, o2 = 34 * CH, o3 = 43 * CH;
 };
 
 // reflected (symmetric-pad) offsets of the 3x3 coarse and 5x5 fine windows of pixel (r, c)
@@ -100,27 +112,79 @@ __device__ __forceinline__ double featp(const Imgs &I, const Px &P, int f, int i
     return I.p3[img * I.img_stride_f + P.yf[k / 5] + P.xf[k % 5] + ch];
   }
 }
-template <int CH>
-__device__ __forceinline__ double feat(const Imgs &I, int f, int r, int c, int img) {
-  int part, k, ch;
-  if (f < 9 * CH) {
-    part = 0; k = f / CH; ch = f % CH;
-  } else if (f < 34 * CH) {
-    part = 1; k = (f - 9 * CH) / CH; ch = (f - 9 * CH) % CH;
-  } else if (f < 43 * CH) {
-    part = 2; k = (f - 34 * CH) / CH; ch = (f - 34 * CH) % CH;
+// feature f of pixel (r, c) for windows w (Geo<CH>{} or the window call's NbhdGeo): parts in the
+// reference's order, each row-major and channel-minor, symmetric padding (ia_reflect takes any
+// reach: periodic for images smaller than the pad); part 3 only reaches its first n_lg^2 / 2 cells
+template <class W>
+__device__ __forceinline__ double win_feat(const W &w, const Imgs &I, int f, int r, int c, int img) {
+  int part, k, chn;
+  if (f < w.o1) {
+    part = 0; k = f / w.ch; chn = f % w.ch;
+  } else if (f < w.o2) {
+    part = 1; k = (f - w.o1) / w.ch; chn = (f - w.o1) % w.ch;
+  } else if (f < w.o3) {
+    part = 2; k = (f - w.o2) / w.ch; chn = (f - w.o2) % w.ch;
   } else {
-    part = 3; k = (f - 43 * CH) / CH; ch = (f - 43 * CH) % CH;
+    part = 3; k = (f - w.o3) / w.ch; chn = (f - w.o3) % w.ch;
   }
-  if (part == 0 || part == 2) {  // 3x3 at (floor(r/2), floor(c/2)) of the padded coarse level
-    int y = ia_reflect((r >> 1) + k / 3 - 1, I.hc), x = ia_reflect((c >> 1) + k % 3 - 1, I.wc);
+  if (part == 0 || part == 2) {  // n_sm x n_sm at (floor(r/2), floor(c/2)) of the padded coarse level
+    const int y = ia_reflect((r >> 1) + k / w.n_sm - w.p_s, I.hc), x = ia_reflect((c >> 1) + k % w.n_sm - w.p_s, I.wc);
     const double *b = part == 0 ? I.p0 : I.p2 + img * I.img_stride_c;
-    return b[((int64_t)y * I.wc + x) * CH + ch];
-  } else {  // 5x5 at (r, c) of the padded fine level (part 3 only reaches k < 12)
-    int y = ia_reflect(r + k / 5 - 2, I.h), x = ia_reflect(c + k % 5 - 2, I.w);
-    const double *b = part == 1 ? I.p1 : I.p3 + img * I.img_stride_f;
-    return b[((int64_t)y * I.w + x) * CH + ch];
+    return b[((int64_t)y * I.wc + x) * w.ch + chn];
   }
+  const int y = ia_reflect(r + k / w.n_lg - w.p_l, I.h), x = ia_reflect(c + k % w.n_lg - w.p_l, I.w);
+  const double *b = part == 1 ? I.p1 : I.p3 + img * I.img_stride_f;
+  return b[((int64_t)y * I.w + x) * w.ch + chn];
+}
+
+// ------------------------------------------------------------------------------------------
+// the causal window rule (best_coherence_match, algorithms.py:92-130), written once for every
+// level path: pad = p_l as a constant (Pad2: the default 5x5) or a run-time int (the window call,
+// the index's coherence batch).  Integer arithmetic on loaded values only: the loads of s / im
+// stay with the callers, whose placement of them differs on purpose.
+// ------------------------------------------------------------------------------------------
+typedef std::integral_constant<int, 2> Pad2;
+template <class P>
+__host__ __device__ constexpr int causal_cells(P pad) {  // cells of the (pad + 1) x (2 pad + 1) window
+  return (pad + 1) * (2 * pad + 1);
+}
+// cell k (product(rows, cols) order) of pixel (r, c), raster index qi, in a level bw wide: its
+// pixel and raster index; ok: inside the level and raster-earlier.  Ix, the type of qi: int on
+// the level paths, int64_t where the pixel is the caller's and unchecked (the coherence batch)
+template <class Ix>
+struct CausalCell {
+  int nr, nc;
+  Ix nb;
+  bool ok;
+};
+template <class P, class Ix>
+__device__ __forceinline__ CausalCell<Ix> causal_cell(P pad, int bw, int r, int c, Ix qi, int k) {
+  const int wd = 2 * pad + 1;
+  CausalCell<Ix> n;
+  n.nr = r - pad + k / wd;
+  n.nc = c - pad + k % wd;
+  n.ok = n.nr >= 0 && n.nc >= 0 && n.nc < bw && (Ix)n.nr * bw + n.nc < qi;
+  n.nb = n.ok ? (Ix)n.nr * bw + n.nc : 0;
+  return n;
+}
+// the source (sr, sc) of neighbour (nr, nc) shifted by its offset to the pixel (r, c): the pixel,
+// and ok: inside A.  Its A' image plays no part, so a caller may load im[nb] after the test.
+struct ShiftedSrc {
+  int tr, tc;
+  bool ok;
+};
+__device__ __forceinline__ ShiftedSrc shifted_src(int ah, int aw, int sr, int sc, int r, int c, int nr, int nc) {
+  ShiftedSrc t;
+  t.tr = sr + r - nr;
+  t.tc = sc + c - nc;
+  t.ok = t.tr >= 0 && t.tr < ah && t.tc >= 0 && t.tc < aw;
+  return t;
+}
+// DB row of pixel (tr, tc) of A' image img.  Row: int on the level paths (their rows are int32),
+// int64_t where img is the caller's and unchecked (the coherence batch)
+template <class Row = int>
+__device__ __forceinline__ Row src_row(int ah, int aw, int img, int tr, int tc) {
+  return ((Row)img * ah + tr) * aw + tc;
 }
 
 // the B side of job jp as the four images its query rows read (B-side FeatDesc parts)
@@ -206,6 +270,15 @@ __device__ __forceinline__ bool kappa_ambiguous(double ya, double da, double yc,
   if (ya == yc) return (ac <= aa * kf) != dec;  // one value: pow rounds both the same way
   return ((ac <= da * kf) != dec) || ((dc <= aa * kf) != dec) || ((ac <= aa * kf) != dec);
 }
+// The kappa rule (image_analogies.py:206) on the two norms y = cr_sqrt(blas_dot_sq(...)) of the
+// approximate and the coherence match: compute_distance = norm(x)**2; true: the coherence match
+// wins.  kamb: the decision would flip under libm pow (above).  (The roots are the callers': one
+// merge takes both on every lane, the finish one per lane before the exchange.)
+__device__ __forceinline__ bool kappa_rule(double y_app, double y_coh, double kf, bool *kamb) {
+  const double d_app = y_app * y_app, d_coh = y_coh * y_coh;
+  *kamb = kappa_ambiguous(y_app, d_app, y_coh, d_coh, kf);
+  return d_coh <= d_app * kf;
+}
 
 // x.x in the summation order of numpy's dot (x.dot(x) inside np.linalg.norm(ord=2), i.e.
 // compute_distance, algorithms.py:133-135) on the host that produced the golden vectors: OpenBLAS
@@ -214,11 +287,14 @@ __device__ __forceinline__ bool kappa_ambiguous(double ya, double da, double yc,
 // blocks into four 8-lane accumulators, whose halves are added into four 4-lane accumulators
 // that take any remaining 16-wide block, then ((a0 + a1) + a2) + a3 per lane and
 // (l0 + l2) + (l1 + l3); the tail N - n1 elements are fused into the running sum.
-template <int N, class X>
-__device__ __forceinline__ double blas_dot_sq(X &&x) {
-  constexpr int N1 = N & ~15, N32 = N1 & ~31;
+// The length is a constant (std::integral_constant: everything unrolls) or a run-time int (the
+// window call's D: the 32-wide, 16-wide and tail loops stay loops, no run-time unrolling).
+template <class L, class X>
+__device__ __forceinline__ double blas_dot_sq(L len, X &&x) {
+  constexpr int U = std::is_same<L, int>::value ? 1 : 16;  // outer-loop unroll: none / all (<= 10 trips)
+  const int N = len, N1 = N & ~15, N32 = N1 & ~31;
   double acc[4][4];
-  if constexpr (N32 > 0) {
+  if (N32 > 0) {
     double z[4][8];
 #pragma unroll
     for (int k = 0; k < 4; k++)
@@ -227,7 +303,7 @@ __device__ __forceinline__ double blas_dot_sq(X &&x) {
         const double v = x(8 * k + l);
         z[k][l] = v * v;  // fma(v, v, 0)
       }
-#pragma unroll
+#pragma unroll U
     for (int i = 32; i < N32; i += 32)
 #pragma unroll
       for (int k = 0; k < 4; k++)
@@ -246,7 +322,7 @@ __device__ __forceinline__ double blas_dot_sq(X &&x) {
 #pragma unroll
       for (int l = 0; l < 4; l++) acc[k][l] = 0.;
   }
-#pragma unroll
+#pragma unroll U
   for (int i = N32; i < N1; i += 16)
 #pragma unroll
     for (int k = 0; k < 4; k++)
@@ -256,18 +332,22 @@ __device__ __forceinline__ double blas_dot_sq(X &&x) {
         acc[k][l] = __builtin_fma(v, v, acc[k][l]);
       }
   double dot = 0.;
-  if constexpr (N1 > 0) {
+  if (N1 > 0) {
     double sl[4];
 #pragma unroll
     for (int l = 0; l < 4; l++) sl[l] = ((acc[0][l] + acc[1][l]) + acc[2][l]) + acc[3][l];
     dot = (sl[0] + sl[2]) + (sl[1] + sl[3]);
   }
-#pragma unroll
+#pragma unroll U
   for (int f = N1; f < N; f++) {
     const double v = x(f);
     dot = __builtin_fma(v, v, dot);
   }
   return dot;
+}
+template <int N, class X>
+__device__ __forceinline__ double blas_dot_sq(X &&x) {
+  return blas_dot_sq(std::integral_constant<int, N>{}, x);
 }
 
 template <int N, class T>
@@ -393,7 +473,8 @@ __device__ __forceinline__ double cert_theta(const MergeArgs &a, double R, doubl
 // Both distances of DB row `row` against query q from ONE set of feature loads (the row of the
 // fp64 DB, K1b; q and w staged in LDS by the caller):
 //   unw = ((a - q)**2).sum()  in numpy's pairwise order (NN rerank / coherence ranking)
-//   wsq = sum(((a - q) * w)**2) sequentially (compute_distance before its sqrt / square)
+//   wsq = sum(((a - q) * w)**2) in the OpenBLAS ddot order, blas_dot_sq (compute_distance before
+//         its sqrt / square)
 template <int CH>
 __device__ __forceinline__ void row_dists(const double *__restrict__ db64, int row, const double *q, const double *w,
                                           double &unw, double &wsq) {

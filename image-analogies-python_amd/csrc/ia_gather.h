@@ -38,13 +38,15 @@ struct CausalNb {
   bool ok;
 };
 __device__ __forceinline__ CausalNb causal_nb(const LevelGeo &g, int r, int c, int qi, int lane, bool nnl) {
+  constexpr int NC = causal_cells(Pad2{});
   CausalNb n{0, 0, 0, 0, false};
-  if (qi > 0 && (lane < 15 || nnl)) {
-    n.k = lane < 15 ? lane : lane - 15;
-    n.nr = r - 2 + n.k / 5;
-    n.nc = c - 2 + n.k % 5;
-    if (n.nr >= 0 && n.nc >= 0 && n.nc < g.bw && n.nr * g.bw + n.nc < qi) {
-      n.nb = n.nr * g.bw + n.nc;
+  if (qi > 0 && (lane < NC || nnl)) {
+    n.k = lane < NC ? lane : lane - NC;
+    const auto cl = causal_cell(Pad2{}, g.bw, r, c, qi, n.k);
+    n.nr = cl.nr;
+    n.nc = cl.nc;
+    if (cl.ok) {
+      n.nb = cl.nb;
       n.ok = true;
     }
   }
@@ -61,7 +63,7 @@ __device__ __forceinline__ double feat_q1(const Imgs &B, int f, int r, int c, co
       return B.p3[(int64_t)y * B.w + x];
     }
   }
-  return feat<1>(B, f, r, c, 0);
+  return win_feat(Geo<1>{}, B, f, r, c, 0);
 }
 
 // owner-computes sharded step (XOPub): query m's fragments (16 h16x8 pieces from LDS, one store
@@ -221,20 +223,15 @@ __device__ __forceinline__ QPre qpre_load(const LevelGeo &g, const StepDesc &sn,
   p.on = true;
   const QPix px = ia_qpix(sn, g.bw, m);
   const int r = px.r, c = px.c;
-  if (lane < D) p.v = feat<1>(B, lane, r, c, 0);
-  if (px.qi > 0 && lane < 15) {
-    const int nr = r - 2 + lane / 5, nc = c - 2 + lane % 5;
-    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < px.qi) {
-      const int nb = nr * g.bw + nc;
-      p.sr = jp.s[2 * nb];
-      p.sc = jp.s[2 * nb + 1];
-      p.si = jp.im[nb];
-    }
+  if (lane < D) p.v = win_feat(Geo<1>{}, B, lane, r, c, 0);
+  // lane k < 15 and, with exact NN rows kept, lane 15 + k: causal cell k (causal_nb's lane roles)
+  const CausalNb n = causal_nb(g, r, c, px.qi, lane, jp.nn && lane >= 15 && lane < 30);
+  if (n.ok && lane < 15) {
+    p.sr = jp.s[2 * n.nb];
+    p.sc = jp.s[2 * n.nb + 1];
+    p.si = jp.im[n.nb];
   }
-  if (px.qi > 0 && jp.nn && lane >= 15 && lane < 30) {
-    const int k = lane - 15, nr = r - 2 + k / 5, nc = c - 2 + k % 5;
-    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < px.qi) p.nn = jp.nn[nr * g.bw + nc];
-  }
+  if (n.ok && lane >= 15) p.nn = jp.nn[n.nb];
   return p;
 }
 
@@ -253,8 +250,8 @@ __device__ __forceinline__ int ucand_row(const LevelGeo &g, int r, int c, int nr
       sc = (int)(rem - (unsigned)sr * (unsigned)g.aw);
     }
   }
-  const int tr = sr + r - nr, tc = sc + c - nc;
-  return (sr >= 0 && tr >= 0 && tr < g.ah && tc >= 0 && tc < g.aw) ? (si * g.ah + tr) * g.aw + tc : -1;
+  const ShiftedSrc t = shifted_src(g.ah, g.aw, sr, sc, r, c, nr, nc);
+  return (sr >= 0 && t.ok) ? src_row(g.ah, g.aw, si, t.tr, t.tc) : -1;
 }
 
 // K2p's work for one query m of step sd (one wave): q64, qn2, fragments, pruning record (also
@@ -368,7 +365,7 @@ __device__ __forceinline__ void gather_h_query_fused(const LevelGeo &g, const St
       bslot(B, f - 43, r, c, y, x);
         v = (y == h.r0 && x == h.c0) ? h.v0 : (y == h.r1 && x == h.c1) ? h.v1 : B.p3[(int64_t)y * B.w + x];
       } else {
-        v = feat<1>(B, f, r, c, 0);
+        v = win_feat(Geo<1>{}, B, f, r, c, 0);
       }
       q64[(int64_t)m * D + f] = v;
       const double qc = v - mu_part[feat_part<1>(f)];

@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(IA_WG) k_gather_query(LevelGeo g, StepDesc sd,
   double ss = 0.;
   for (int f = lane; f < G::DP; f += IA_WAVE) {
     if (f < G::D) {
-      const double v = feat<CH>(B, f, r, c, 0);
+      const double v = win_feat(Geo<CH>{}, B, f, r, c, 0);
       q64[(int64_t)m * G::D + f] = v;
       const double qc = v - mu_part[feat_part<CH>(f) * CH + feat_ch<CH>(f)];
       ss += qc * qc;
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(IA_PQ_WG) k_gather_query_h(LevelGeo g, StepDes
   double ss = 0.;
   for (int f = lane; f < KD; f += IA_WAVE) {
     if (f < D) {
-      const double v = feat<CH>(B, f, r, c, 0);
+      const double v = win_feat(Geo<CH>{}, B, f, r, c, 0);
       q64[(int64_t)m * D + f] = v;
       const double qc = v - mu_part[feat_part<CH>(f) * CH + feat_ch<CH>(f)];
       ss += qc * qc;

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <string>
@@ -231,8 +232,48 @@ int index_check_queries(const ia_index *x, const std::string &who, const double 
 // allocates x->q, x->qn2 and x->qf for the batches of nq queries; every entry point's first
 // allocation, before it takes a device pointer of the index
 int index_reserve_batch(ia_index *x, int64_t nq);
+// The dense rules of the index, which the window level (ia_level_nbhd.cpp) runs on its own rows.
+// Scan decomposition of n_tiles DB tiles: tiles per workgroup, workgroups.
+inline void dense_geometry(int n_tiles, int *tpw, int *nwg) {
+  *tpw = std::max(4, (n_tiles + IA_WG_TARGET - 1) / IA_WG_TARGET);
+  *nwg = (n_tiles + *tpw - 1) / *tpw;
+}
+// prescale of the centred fp32 copy: 2^-e with the largest centred |value| amax in [2^(e-1), 2^e), so
+// the fp32 scan sees values in [0.5, 1) (|e| <= 500 keeps sc^2 a normal fp64; an all-equal DB keeps 1)
+inline double dense_prescale(double amax) {
+  return amax > 0. ? std::ldexp(1.0, -std::max(-500, std::min(500, std::ilogb(amax) + 1))) : 1.;
+}
+// the arguments of a dense merge (k_merge_dense, _knn) over the whole unpruned, unsharded DB
+inline MergeArgs dense_merge_args(const float4 *rec, const float *recT, const double *qn2, const unsigned *Rbits, int nwg,
+                                  int tpw, int n_tiles, int64_t n, int KH) {
+  MergeArgs ma;
+  ma.db64 = nullptr;
+  ma.rec = rec;
+  ma.recT = recT;
+  ma.q64 = nullptr;
+  ma.qn2 = qn2;
+  ma.Rbits = Rbits;
+  ma.nwg = nwg;
+  ma.tpw = tpw;
+  ma.pos0 = 0;
+  ma.pos_end = n_tiles * IA_TILE;
+  ma.NT = n_tiles;
+  ma.NA = (int)n;
+  ma.pos2row = nullptr;
+  ma.rr = 0;
+  ma.qinfo = nullptr;
+  ma.boxes = nullptr;
+  ma.ufac = 0.;
+  ma.img_rows = 0;
+  ma.eps_c = ia_eps_c(2 * KH);
+  ma.eps_a = 0.;
+  return ma;
+}
 // the merge arguments of an index: its records (x->rec, x->recT, x->qn2 as allocated now) over the whole DB
-MergeArgs index_merge_args(const ia_index *x);
+inline MergeArgs index_merge_args(const ia_index *x) {
+  return dense_merge_args(x->rec.as<float4>(), x->recT.as<float>(), x->qn2.as<double>(), x->Rbits.as<unsigned>(), x->nwg,
+                          x->tpw, x->n_tiles, x->n, x->KH);
+}
 // per batch of IA_INDEX_BATCH queries: uploads the queries b0 .. b0 + nb to x->q (q = nullptr: copies
 // the index's own rows b0 .. b0 + nb there, on the device), builds x->qn2 and
 // x->qf (Mpad = nb padded to qtt query tiles), then body(b0, nb, Mpad, qtt), which enqueues its scans
@@ -240,8 +281,8 @@ MergeArgs index_merge_args(const ia_index *x);
 int index_for_batches(ia_index *x, const double *q, int64_t nq, const std::function<int(int64_t, int, int, int)> &body);
 // the query tiles [qta, qtb) in launches of at most ia_k3_qtmax(KH): launch(first tile, tiles)
 template <class F>
-void index_scan_tiles(const ia_index *x, int qta, int qtb, F &&launch) {
-  const int qtmax = ia_k3_qtmax(x->KH);
+void index_scan_tiles(int KH, int qta, int qtb, F &&launch) {
+  const int qtmax = ia_k3_qtmax(KH);
   for (int qt0 = qta; qt0 < qtb; qt0 += qtmax) launch(qt0, std::min(qtmax, qtb - qt0));
 }
 

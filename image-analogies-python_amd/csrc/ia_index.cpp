@@ -22,31 +22,6 @@ int index_check_queries(const ia_index *x, const std::string &who, const double 
   return IA_OK;
 }
 
-MergeArgs index_merge_args(const ia_index *x) {
-  MergeArgs ma;
-  ma.db64 = nullptr;
-  ma.rec = x->rec.as<float4>();
-  ma.recT = x->recT.as<float>();
-  ma.q64 = nullptr;
-  ma.qn2 = x->qn2.as<double>();
-  ma.Rbits = x->Rbits.as<unsigned>();
-  ma.nwg = x->nwg;
-  ma.tpw = x->tpw;
-  ma.pos0 = 0;
-  ma.pos_end = x->n_tiles * IA_TILE;
-  ma.NT = x->n_tiles;
-  ma.NA = (int)x->n;
-  ma.pos2row = nullptr;
-  ma.rr = 0;
-  ma.qinfo = nullptr;
-  ma.boxes = nullptr;
-  ma.ufac = 0.;
-  ma.img_rows = 0;
-  ma.eps_c = ia_eps_c(2 * x->KH);
-  ma.eps_a = 0.;
-  return ma;
-}
-
 int index_reserve_batch(ia_index *x, int64_t nq) {
   const int64_t bmax = std::min(nq, IA_INDEX_BATCH), bpad = tile_pad(bmax);
   int rc;
@@ -74,7 +49,7 @@ int index_for_batches(ia_index *x, const double *q, int64_t nq, const std::funct
 
 // the top-2 scan of a batch's nb queries (qtt query tiles) into x->rec / x->recT
 static void index_scan_top2(ia_index *x, int nb, int qtt) {
-  index_scan_tiles(x, 0, qtt, [&](int qt0, int qt) {
+  index_scan_tiles(x->KH, 0, qtt, [&](int qt0, int qt) {
     ia_launch_k3(x->KH, qt, x->db.as<float4>(), x->qf.as<float4>(), x->n_tiles, x->tpw, qt0, nb, x->nwg, 0, x->n_tiles,
                  x->rec.as<float4>(), x->recT.as<float>(), x->ctx->st);
   });
@@ -203,16 +178,13 @@ int ia_index_build(ia_ctx *c, const double *pts, int64_t n, int d, ia_index **ou
   x->d = d;
   x->KH = KH;
   x->n_tiles = (int)((n + IA_TILE - 1) / IA_TILE);
-  x->tpw = std::max(4, (x->n_tiles + IA_WG_TARGET - 1) / IA_WG_TARGET);
-  x->nwg = (x->n_tiles + x->tpw - 1) / x->tpw;
+  dense_geometry(x->n_tiles, &x->tpw, &x->nwg);
   // column means (host, fixed order): centre the fp32 copy, shrinking the MFMA error bound
   std::vector<double> mu(d, 0.);
   for (int64_t i = 0; i < n; i++)
     for (int f = 0; f < d; f++) mu[f] += pts[i * d + f];
   for (int f = 0; f < d; f++) mu[f] /= (double)n;
-  // prescale: 2^-e with the largest centred |value| in [2^(e-1), 2^e), so the fp32 scan sees values
-  // in [0.5, 1) (|e| <= 500 keeps sc^2 a normal fp64; an all-equal DB keeps sc = 1)
-  double amax = 0.;
+  double amax = 0.;  // the largest centred |value|: the prescale
   for (int64_t i = 0; i < n; i++)
     for (int f = 0; f < d; f++) amax = std::fmax(amax, std::fabs(pts[i * d + f] - mu[f]));
   if (!std::isfinite(amax)) {  // (fmax drops a NaN: the means carry it)
@@ -224,7 +196,7 @@ int ia_index_build(ia_ctx *c, const double *pts, int64_t n, int d, ia_index **ou
       delete x;
       return fail(IA_EINVAL, "ia_index_build: rows must be finite (and their column sums too)");
     }
-  x->sc = amax > 0. ? std::ldexp(1.0, -std::max(-500, std::min(500, std::ilogb(amax) + 1))) : 1.;
+  x->sc = dense_prescale(amax);
   x->mu_h = mu;
   int rc;
   if ((rc = x->pts.ensure((size_t)n * d * 8)) || (rc = x->db.ensure((size_t)x->n_tiles * IA_TILE * 2 * KH * 4)) ||

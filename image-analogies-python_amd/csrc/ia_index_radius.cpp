@@ -64,7 +64,7 @@ int radius_run(ia_index *x, const std::string &who, const double *q, int64_t nq,
     HIP_TRY(hipMemcpyAsync(x->r_rad.p, radius + b0, (size_t)nb * 8, hipMemcpyHostToDevice, c->st));
     ia_launch_k3r_thresholds(x->r_rad.as<double>(), x->qn2.as<double>(), x->Rbits.as<unsigned>(), nb, Mpad, x->sc * x->sc,
                              ia_eps_c(2 * x->KH), x->r_thr.as<float2>(), c->st);
-    index_scan_tiles(x, 0, qtt, [&](int qt0, int qt) {
+    index_scan_tiles(x->KH, 0, qtt, [&](int qt0, int qt) {
       ia_launch_k3r_count(x->KH, qt, db, qf, thr, NT, x->tpw, qt0, nb, nwg, x->r_cnt.as<uint2>(), c->st);
     });
     ia_launch_k3r_offsets(x->r_cnt.as<uint2>(), nb, nwg, count_only, x->r_seg.as<uint2>(), x->r_ts.as<uint2>(), c->st);
@@ -100,7 +100,7 @@ int radius_run(ia_index *x, const std::string &who, const double *q, int64_t nq,
       HIP_TRY(hipMemcpyAsync(x->r_soff.as<unsigned>() + j0, &soff[j0], (size_t)(j1 - j0 + 1) * 4, hipMemcpyHostToDevice, c->st));
       if (sum > 0) {
         // the query tiles that hold [j0, j1)
-        index_scan_tiles(x, j0 / IA_TILE, (j1 - 1) / IA_TILE + 1, [&](int qt0, int qt) {
+        index_scan_tiles(x->KH, j0 / IA_TILE, (j1 - 1) / IA_TILE + 1, [&](int qt0, int qt) {
           ia_launch_k3r_fill(x->KH, qt, count_only, db, qf, thr, NT, x->tpw, qt0, j0, j1, nwg, x->r_seg.as<uint2>(), qoff_d,
                              x->r_wr.as<int>(), c->st);
         });

@@ -231,11 +231,12 @@ struct JobSet {   // host side: what the launchers dispatch on
 struct QPix {
   int job, r, c, qi;           // job, pixel (r, c) and its raster index in the B level
 };
-__host__ __device__ inline QPix ia_qpix(const StepDesc &sd, int bw, int m) {
+// (skew = p_l + 1: the default windows' 3, or the window call's)
+__host__ __device__ inline QPix ia_qpix(const StepDesc &sd, int bw, int m, int skew = 3) {
   QPix p;
   p.job = m / sd.M;
   p.r = sd.r0 + (m - p.job * sd.M);
-  p.c = sd.t - 3 * p.r;
+  p.c = sd.t - skew * p.r;
   p.qi = p.r * bw + p.c;
   return p;
 }

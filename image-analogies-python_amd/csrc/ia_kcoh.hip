@@ -28,24 +28,21 @@ __device__ __forceinline__ double kcoh_dist(const double *__restrict__ db64, int
   });
 }
 
-// the base row of causal cell k < 15 (coherence_pick's: neighbour (r - 2 + k / 5, c - 2 + k % 5)) of
-// pixel (r, c), raster index qi: the neighbour's source shifted by the offset, or -1 (no such
-// neighbour before qi, or the shifted source outside A)
+// the base row of causal cell k < 15 (coherence_pick's) of pixel (r, c), raster index qi: the
+// neighbour's source shifted by the offset, or -1 (no such neighbour before qi, or the shifted
+// source outside A)
 __device__ __forceinline__ int kcoh_base_row(const LevelGeo &g, const int32_t *__restrict__ s, const int32_t *__restrict__ im,
                                              int r, int c, int qi, int k) {
-  const int nr = r - 2 + k / 5, nc = c - 2 + k % 5;
-  if (nr < 0 || nc < 0 || nc >= g.bw) return -1;
-  const int nb = nr * g.bw + nc;
-  if (nb >= qi) return -1;
-  const int tr = s[2 * nb] + r - nr, tc = s[2 * nb + 1] + c - nc;
-  if (tr < 0 || tr >= g.ah || tc < 0 || tc >= g.aw) return -1;
-  return (im[nb] * g.ah + tr) * g.aw + tc;
+  const auto n = causal_cell(Pad2{}, g.bw, r, c, qi, k);
+  if (!n.ok) return -1;
+  const ShiftedSrc t = shifted_src(g.ah, g.aw, s[2 * n.nb], s[2 * n.nb + 1], r, c, n.nr, n.nc);
+  return t.ok ? src_row(g.ah, g.aw, im[n.nb], t.tr, t.tc) : -1;
 }
 // the pixel has a base row; cell 11, the left neighbour, first: it settles nearly every pixel
 __device__ __forceinline__ bool kcoh_has_base(const LevelGeo &g, const int32_t *__restrict__ s, const int32_t *__restrict__ im,
                                               int r, int c, int qi) {
   if (kcoh_base_row(g, s, im, r, c, qi, 11) >= 0) return true;
-  for (int k = 0; k < 15; k++)
+  for (int k = 0; k < causal_cells(Pad2{}); k++)
     if (kcoh_base_row(g, s, im, r, c, qi, k) >= 0) return true;
   return false;
 }
@@ -62,7 +59,7 @@ template <int CH, class JS>
 __device__ __forceinline__ void kcoh_gather(const LevelGeo &g, Imgs B, const JS &jobs, const QPix &px, const JobPtrs &jp,
                                             int lane, double *q) {
   if constexpr (!JS::single) B = job_imgs(B, jp);  // single job: B already holds its images
-  for (int f = lane; f < Geo<CH>::D; f += IA_WAVE) q[f] = feat<CH>(B, f, px.r, px.c, 0);
+  for (int f = lane; f < Geo<CH>::D; f += IA_WAVE) q[f] = win_feat(Geo<CH>{}, B, f, px.r, px.c, 0);
   __builtin_amdgcn_wave_barrier();  // written by this wave's lanes, read by all of them
 }
 
@@ -100,7 +97,7 @@ __device__ void kcoh_scan_pixel(const LevelGeo &g, const StepDesc &sd, const Img
   wave_min_di(bd, bi);
   if (lane == 0) ks.cnt[m] = 0u;
   // (stats word as below: no candidates, one fallback)
-  finish_pixel<CH>(g, A, db64, px.r, px.c, bi, q, jp.s, jp.im, jp.Bp, jp.weights, jp.kf, jp.pstat, 1u << 16);
+  finish_pixel(LevelRows<CH>{db64}, g, A, px.r, px.c, bi, q, jp.s, jp.im, jp.Bp, jp.weights, jp.kf, jp.pstat, 1u << 16);
 }
 
 template <int CH, class JS>
@@ -136,7 +133,7 @@ __global__ void __launch_bounds__(IA_PQ_WG) k_kcoh_step(LevelGeo g, StepDesc sd,
   const QPix px = ia_qpix(sd, g.bw, m);
   const JobPtrs jp = jobs.get(px.job);
   const int r = px.r, c = px.c, qi = px.qi;
-  const int b = lane < 15 ? kcoh_base_row(g, jp.s, jp.im, r, c, qi, lane) : -1;
+  const int b = lane < causal_cells(Pad2{}) ? kcoh_base_row(g, jp.s, jp.im, r, c, qi, lane) : -1;
   const unsigned long long bal = __ballot(b >= 0);
   const int nbase = __popcll(bal);  // <= 12: the causal cells
   if (nbase == 0) return;           // the scan waves find its exact NN and finish it
@@ -156,7 +153,7 @@ __global__ void __launch_bounds__(IA_PQ_WG) k_kcoh_step(LevelGeo g, StepDesc sd,
   }
   wave_min_di(bd, bi);
   // stats word as K4's (JobPtrs::pstat): bits 0-15 the candidates computed, bit 16 a fallback
-  finish_pixel<CH>(g, A, db64, r, c, bi, q, jp.s, jp.im, jp.Bp, jp.weights, jp.kf, jp.pstat, (unsigned)ncand);
+  finish_pixel(LevelRows<CH>{db64}, g, A, r, c, bi, q, jp.s, jp.im, jp.Bp, jp.weights, jp.kf, jp.pstat, (unsigned)ncand);
 }
 
 // pre-pass: every entry of sim (n of them) is a DB row

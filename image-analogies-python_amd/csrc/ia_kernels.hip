@@ -67,7 +67,7 @@ __device__ __forceinline__ void merge_fused(const LevelGeo &g, const StepDesc &s
 #endif
   IA_STAMP(0);
   // RPL: records per lane (nwg <= 64 RPL); 4 for the split-f16 scans (<= 256 workgroups)
-  constexpr int NCOH = 15, NRR = IA_WAVE - NCOH;  // lanes for coherence / rerank candidates
+  constexpr int NCOH = causal_cells(Pad2{}), NRR = IA_WAVE - NCOH;  // lanes for coherence / rerank candidates
   const int lane = threadIdx.x & 63;
   const int r = px.r, c = px.c, qi = px.qi;
   int32_t *__restrict__ s = jp.s, *__restrict__ im = jp.im;
@@ -127,16 +127,15 @@ __device__ __forceinline__ void merge_fused(const LevelGeo &g, const StepDesc &s
   }
   int crow = -1, cpr = -1, cpc = -1, cim = 0;
   if (qi > 0 && lane < NCOH) {  // best_coherence_match candidates, product(rows, cols) order
-    const int nr = r - 2 + lane / 5, nc = c - 2 + lane % 5;
-    if (nr >= 0 && nc >= 0 && nc < g.bw && nr * g.bw + nc < qi) {
-      const int nb = nr * g.bw + nc;
-      const int tr = s[2 * nb] + r - nr, tc = s[2 * nb + 1] + c - nc;
-      const int ti = im[nb];
-      if (tr >= 0 && tr < g.ah && tc >= 0 && tc < g.aw) {
-        cpr = tr;
-        cpc = tc;
+    const auto n = causal_cell(Pad2{}, g.bw, r, c, qi, lane);
+    if (n.ok) {
+      const ShiftedSrc t = shifted_src(g.ah, g.aw, s[2 * n.nb], s[2 * n.nb + 1], r, c, n.nr, n.nc);
+      const int ti = im[n.nb];  // (issued with s, before the bounds test)
+      if (t.ok) {
+        cpr = t.tr;
+        cpc = t.tc;
         cim = ti;
-        crow = (ti * g.ah + tr) * g.aw + tc;
+        crow = src_row(g.ah, g.aw, ti, t.tr, t.tc);
       }
     }
   }
@@ -351,13 +350,9 @@ __device__ __forceinline__ void merge_fused(const LevelGeo &g, const StepDesc &s
       if (lane == 0) row_dists<CH>(a.db64, bi, qs, ws, u, wq);
       wsq_app = readlane_d(wq, 0);
     }
-    // compute_distance = norm(x)**2 = sqrt(sum x^2)**2 ; kappa rule image_analogies.py:206
-    const double y_app = cr_sqrt(wsq_app), y_coh = cr_sqrt(wsq_coh);
-    const double d_app = y_app * y_app, d_coh = y_coh * y_coh;
-    kamb = kappa_ambiguous(y_app, d_app, y_coh, d_coh, kf);
     dbg_app = wsq_app;  // the host finishes compute_distance as np.sqrt(v) ** 2 (libm pow)
     dbg_coh = wsq_coh;
-    if (d_coh <= d_app * kf) {
+    if (kappa_rule(cr_sqrt(wsq_app), cr_sqrt(wsq_coh), kf, &kamb)) {
       img = kim;
       pr = kpr;
       pc = kpc;
@@ -392,8 +387,9 @@ __device__ __forceinline__ void merge_fused(const LevelGeo &g, const StepDesc &s
       o[0] = app_pr;
       o[1] = app_pc;
       o[2] = app_img;
-      o[3] = has_coh ? r - 2 + kk / 5 : 0;
-      o[4] = has_coh ? c - 2 + kk % 5 : 0;
+      const auto n = causal_cell(Pad2{}, g.bw, r, c, qi, has_coh ? kk : 0);  // r_star
+      o[3] = has_coh ? n.nr : 0;
+      o[4] = has_coh ? n.nc : 0;
       o[5] = has_coh ? 1 : 0;
       jp.dbg_dist[2 * qi] = dbg_app;
       jp.dbg_dist[2 * qi + 1] = dbg_coh;

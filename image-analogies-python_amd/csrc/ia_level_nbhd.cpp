@@ -62,8 +62,8 @@ int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInpu
   ia_wavefront_shape_pad(g.bh, g.bw, w.p_l, &P.T, &P.Mmax);
   P.Mtmax = P.Mmax * P.J;
   P.Mpad_max = tile_pad(P.Mtmax);
-  // the index's geometry rule (ia_index_build)
-  const int tpw = std::max(4, (g.n_tiles + IA_WG_TARGET - 1) / IA_WG_TARGET), nwg = (g.n_tiles + tpw - 1) / tpw;
+  int tpw, nwg;
+  dense_geometry(g.n_tiles, &tpw, &nwg);
   if ((rc = stage_jobs(c, P, in)) || (rc = c->db64.ensure((size_t)g.NA * D * 8)) || (rc = c->mu.ensure((size_t)D * 8)) ||
       (rc = c->absmax.ensure(4)) || (rc = c->Rbits.ensure(4)) || (rc = c->counters.ensure(5 * 8)) ||
       (rc = c->db.ensure((size_t)g.n_tiles * IA_TILE * 2 * KH * 4)) || (rc = c->q64.ensure((size_t)P.Mtmax * D * 8)) ||
@@ -89,34 +89,12 @@ int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInpu
   bool finite = std::isfinite(amaxf);
   for (int f = 0; f < D; f++) finite = finite && std::isfinite(mu_h[f]);
   if (!finite) return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: the A side must be finite (and its column sums too)");
-  // prescale as ia_index_build's: the largest centred |value| lands in [0.5, 1) (an all-equal DB keeps 1)
-  const double amax = amaxf;
-  const double sc = amax > 0. ? std::ldexp(1.0, -std::max(-500, std::min(500, std::ilogb(amax) + 1))) : 1.;
+  const double sc = dense_prescale(amaxf);
   ia_launch_dense_db(KH, rows, g.NA, D, g.n_tiles, mu, sc, c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
   HIP_TRY(hipEventRecord(c->lv1, c->st));
 
-  MergeArgs ma;
-  ma.db64 = nullptr;
-  ma.rec = c->rec.as<float4>();
-  ma.recT = c->recT.as<float>();
-  ma.q64 = nullptr;
-  ma.qn2 = c->qn2.as<double>();
-  ma.Rbits = c->Rbits.as<unsigned>();
-  ma.nwg = nwg;
-  ma.tpw = tpw;
-  ma.pos0 = 0;
-  ma.pos_end = g.n_tiles * IA_TILE;
-  ma.NT = g.n_tiles;
-  ma.NA = (int)g.NA;
-  ma.pos2row = nullptr;
-  ma.rr = 0;
-  ma.qinfo = nullptr;
-  ma.boxes = nullptr;
-  ma.ufac = 0.;
-  ma.img_rows = 0;
-  ma.eps_c = ia_eps_c(2 * KH);
-  ma.eps_a = 0.;
-  const int qtmax = ia_k3_qtmax(KH);
+  const MergeArgs ma = dense_merge_args(c->rec.as<float4>(), c->recT.as<float>(), c->qn2.as<double>(), c->Rbits.as<unsigned>(),
+                                        nwg, tpw, g.n_tiles, g.NA, KH);
   int64_t scans = 0;
   for (int64_t t = 0; t < P.T; t++) {
     StepDesc sd{(int)t, 0, 0, 0, P.J};
@@ -126,10 +104,11 @@ int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInpu
     sd.Mpad = (int)tile_pad(Mt);
     ia_launch_nbhd_gather(w, sd, in.Bim, in.jobs(), q64, c->st);
     ia_launch_dense_query(KH, q64, Mt, D, sd.Mpad, mu, sc, c->qn2.as<double>(), c->qf.as<float>(), c->st);
-    const int qtt = sd.Mpad / IA_TILE;
-    for (int qt0 = 0; qt0 < qtt; qt0 += qtmax, scans++)  // (index_scan_tiles' blocking)
-      ia_launch_k3(KH, std::min(qtmax, qtt - qt0), c->db.as<float4>(), c->qf.as<float4>(), g.n_tiles, tpw, qt0, Mt, nwg, 0,
-                   g.n_tiles, c->rec.as<float4>(), c->recT.as<float>(), c->st);
+    index_scan_tiles(KH, 0, sd.Mpad / IA_TILE, [&](int qt0, int qt) {
+      ia_launch_k3(KH, qt, c->db.as<float4>(), c->qf.as<float4>(), g.n_tiles, tpw, qt0, Mt, nwg, 0, g.n_tiles,
+                   c->rec.as<float4>(), c->recT.as<float>(), c->st);
+      scans++;
+    });
     ia_launch_merge_dense(ma, rows, D, q64, Mt, sc * sc, idx, c->allwin.as<double>(), c->st);
     ia_launch_nbhd_finish(w, g, sd, in.Aim, in.jobs(), rows, q64, idx, c->st);
   }

@@ -374,20 +374,15 @@ using namespace ia_host;
 
 extern "C" {
 
+// the default windows' wavefront: the window call's (ia_level_nbhd.cpp) at pad 2, i.e. skew 3
 int ia_wavefront_shape(int h, int w, int64_t *steps, int64_t *max_queries) {
   if (h < 1 || w < 1) return fail(IA_EINVAL, "ia_wavefront_shape: empty level");
-  if (steps) *steps = (int64_t)w + 3 * (int64_t)(h - 1);
-  if (max_queries) *max_queries = std::min<int64_t>(h, (w + 2) / 3);
-  return IA_OK;
+  return ia_wavefront_shape_pad(h, w, 2, steps, max_queries);
 }
 
 int ia_wavefront_step(int h, int w, int64_t t, int *r0, int *M) {
   if (h < 1 || w < 1 || t < 0 || t >= (int64_t)w + 3 * (int64_t)(h - 1)) return fail(IA_EINVAL, "ia_wavefront_step: bad step");
-  const int64_t r_lo = std::max<int64_t>(0, (t - w + 1 + 2) / 3);  // ceil((t - w + 1) / 3), t - w + 3 > 0
-  const int64_t r_hi = std::min<int64_t>(h - 1, t / 3);
-  *r0 = (int)r_lo;
-  *M = (int)(r_hi - r_lo + 1);
-  return IA_OK;
+  return ia_wavefront_step_pad(h, w, 2, t, r0, M);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ __global__ void __launch_bounds__(IA_WG) k_finish_level(LevelGeo g, StepDesc sd,
   const QPix px = ia_qpix(sd, g.bw, m);
   const JobPtrs jp = jobs.get(px.job);
   const unsigned prev = jp.pstat ? jp.pstat[px.qi] : 0u;
-  finish_pixel<CH>(g, A, db64, px.r, px.c, bi, q64 + (int64_t)m * Geo<CH>::D, jp.s, jp.im, jp.Bp, jp.weights, jp.kf,
+  finish_pixel(LevelRows<CH>{db64}, g, A, px.r, px.c, bi, q64 + (int64_t)m * Geo<CH>::D, jp.s, jp.im, jp.Bp, jp.weights, jp.kf,
                    jp.pstat, prev, jp.nn);
 }
 
@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(IA_PQ_WG) k_merge_xchg(LevelGeo g, StepDesc sd
     return;
   } else {
     // the coherence pick does not depend on the NN winner: it runs while the peers' winners travel
-    const CohPick ck = coherence_pick<CH>(g, ma.db64, px.r, px.c, q, jp.s, jp.im);
+    const CohPick ck = coherence_pick(LevelRows<CH>{ma.db64}, g, px.r, px.c, q, jp.s, jp.im);
     double bd = DBL_MAX;
     int64_t bi = INT64_MAX;
     bool late = false;
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(IA_PQ_WG) k_merge_xchg(LevelGeo g, StepDesc sd
       bi = 0;
       if (lane == 0) atomicOr(xa.err, 2u);
     }
-    finish_pick<CH>(g, A, ma.db64, px.r, px.c, bi, ck, q, jp.s, jp.im, jp.Bp, jp.weights, jp.kf, jp.pstat, stat, jp.nn);
+    finish_pick(LevelRows<CH>{ma.db64}, g, A, px.r, px.c, bi, ck, q, jp.s, jp.im, jp.Bp, jp.weights, jp.kf, jp.pstat, stat, jp.nn);
   }
 }
 

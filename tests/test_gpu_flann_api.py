@@ -148,6 +148,49 @@ def test_coherence_batch_matches_per_pixel_and_errors():
         algorithms.best_coherence_match_batch(As[level], A_hw, Q[w + 3:w + 4], s[:2], im[:2], pxs[w + 3:w + 4], w, c)
 
 
+def test_coherence_batch_equals_level_debug_records(ctx):
+    """The two users of the causal-window rule that nothing else compares: the default level call
+    (merge_fused, the window as a constant) and ia_coherence_batch at pad 2 (the window at run time).
+    The finest level of the adversarial 'offset' case (A 25 x 19, B 16 x 20, three levels) runs with
+    debug records; an index on that level's fp64 feature rows then gets every pixel with its query
+    row, the level's final s / im and n_s = the level's size.  p_out / img_out / r_out must equal the
+    records' coherence pick and r_star wherever a pixel has one, (-1, -1) / 0 / (0, 0) elsewhere: 320
+    queries, bit for bit.  The oracle's log of this input (checked on the CPU) has both kinds of
+    pixel: 311 with a pick, 8 without besides the level's first."""
+    import adversarial_inputs as AI
+    from ia_amd import _native
+    from oracle import ia_oracle as O
+    z = AI.oracle('offset')
+    L, k = z['L'], z['k']
+    level = L - 1
+    Bp = [x.copy() for x in z['Bp_init']]
+    for lv in range(1, L):
+        dbg = {}
+        s, im = ctx.synthesize_level(z['A_pyr'][lv], z['A_pyr'][lv - 1], [p[lv] for p in z['Ap_pyr']],
+                                     [p[lv - 1] for p in z['Ap_pyr']], z['B_pyr'][lv], z['B_pyr'][lv - 1], Bp[lv - 1],
+                                     Bp[lv], z['weights'], 1 + (2 ** (lv - L)) * k, _native.Stats(), debug=dbg)
+    src = dbg['src']
+    h, w = z['B_pyr'][level].shape
+    a_hw = z['A_pyr'][level].shape
+    assert (h, w) == (16, 20) and a_hw == (25, 19)
+    Bf = O.feature_array(z['B_pyr'], level, True)
+    # (a query row reads only raster-earlier B' pixels of its level: the final state serves every pixel)
+    Q = np.array([O.query_feature(Bf, Bp[level - 1], Bp[level], r, c, w) for r in range(h) for c in range(w)])
+    px = np.array([(r, c) for r in range(h) for c in range(w)], dtype=np.int32)
+    idx = _native.ExactIndex(ctx, O.build_db(z['A_pyr'], z['Ap_pyr'], level))
+    try:
+        p, img, rs = idx.coherence(Q, px, s, im, a_hw, w, 2)
+    finally:
+        idx.close()
+    has = src[:, 5] != 0
+    assert 0 < int(has.sum()) < h * w - 1   # both kinds, besides the first pixel
+    nb = src[:, 3] * w + src[:, 4]
+    ref_p = np.where(has[:, None], s[nb] + px - src[:, 3:5], -1)
+    assert np.array_equal(p, ref_p)
+    assert np.array_equal(img, np.where(has, im[nb], 0))
+    assert np.array_equal(rs, np.where(has[:, None], src[:, 3:5], 0))
+
+
 def test_coherence_per_pixel_matches_oracle():
     """best_coherence_match on a plain As array (no attached index: one upload per call) against
     the oracle's restatement of algorithms.py:92-130 on teacher-forced g32 states."""
