@@ -123,6 +123,16 @@ EXPORTS = {
     'ia_index_set_workspace': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     'ia_index_radius_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'ia_index_destroy': (None, [ctypes.c_void_p]),
+    'ia_kmeans': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
+    'ia_ann_build': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    'ia_ann_lists': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'ia_ann_query': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_void_p, ctypes.c_void_p]),
+    'ia_ann_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'ia_ann_build_ms': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    'ia_ann_destroy': (None, [ctypes.c_void_p]),
     'ia_coherence_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -610,6 +620,90 @@ class ExactIndex(object):
     def close(self):
         if self._h:
             lib().ia_index_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ANN_MAX_LISTS = 4096  # IA_ANN_MAX_LISTS
+
+
+def default_n_lists(n):
+    """the lists of an AnnIndex over n rows when none are asked for: isqrt(n) clamped to 1..ANN_MAX_LISTS"""
+    return max(1, min(ANN_MAX_LISTS, math.isqrt(int(n))))
+
+
+def kmeans(ctx, pts, k, iters=5):
+    """ia_kmeans: the deterministic Lloyd's k-means of include/ia.h (initial centre c = row floor(c n / k),
+    ties to the lower centre, sums in ascending row order).  Returns (centers (k, d) float64, assign (n,)
+    int32, iters_run)."""
+    pts = _c64(pts)
+    if pts.ndim != 2 or pts.shape[0] < 1:
+        raise IAError('kmeans: pts must be a non-empty (n, d) array')
+    n, d = pts.shape
+    k = int(k)
+    centers = np.empty((max(k, 0), d), dtype=np.float64)
+    assign = np.empty(n, dtype=np.int32)
+    run = ctypes.c_int()
+    check(lib().ia_kmeans(ctx.handle, _ptr(pts), n, d, k, int(iters), _ptr(centers), _ptr(assign), ctypes.byref(run)),
+          'ia_kmeans')
+    return centers, assign, run.value
+
+
+class AnnIndex(object):
+    """ia_ann_*: the approximate index: k-means lists whose queries honour `checks`.
+    n_lists = None: default_n_lists(n).  Deterministic; checks = -1 (or >= n) is ExactIndex.query_knn."""
+
+    def __init__(self, ctx, pts, n_lists=None, iters=5):
+        pts = _c64(pts)
+        if pts.ndim != 2 or pts.shape[0] < 1:
+            raise IAError('AnnIndex: pts must be a non-empty (n, d) array')
+        self.ctx = ctx
+        self.n, self.d = pts.shape
+        self.n_lists = default_n_lists(self.n) if n_lists is None else int(n_lists)
+        self._h = ctypes.c_void_p()
+        check(lib().ia_ann_build(ctx.handle, _ptr(pts), self.n, self.d, self.n_lists, int(iters), ctypes.byref(self._h)),
+              'ia_ann_build')
+
+    def query(self, q, k=1, checks=32):
+        """ia_ann_query: (idx (nq, k) int64, dist (nq, k) float64), shaped as ExactIndex.query_knn's"""
+        q = _c64(np.atleast_2d(q))
+        if q.shape[1] != self.d:
+            raise IAError('AnnIndex.query: query width %d != index width %d' % (q.shape[1], self.d))
+        k = int(k)
+        idx = np.empty((q.shape[0], max(k, 0)), dtype=np.int64)
+        dist = np.empty((q.shape[0], max(k, 0)), dtype=np.float64)
+        check(lib().ia_ann_query(self._h, _ptr(q), q.shape[0], k, int(checks), _ptr(idx), _ptr(dist)), 'ia_ann_query')
+        return idx, dist
+
+    def lists(self):
+        """ia_ann_lists: (centers (L, d) float64, sizes (L,) int64, rows (n,) int32: list after list, each ascending)"""
+        centers = np.empty((self.n_lists, self.d), dtype=np.float64)
+        sizes = np.empty(self.n_lists, dtype=np.int64)
+        rows = np.empty(self.n, dtype=np.int32)
+        check(lib().ia_ann_lists(self._h, _ptr(centers), _ptr(sizes), _ptr(rows)), 'ia_ann_lists')
+        return centers, sizes, rows
+
+    def stats(self):
+        """ia_ann_stats: (rows whose distance the last query call computed, lists it probed - both summed over
+        its queries -, k-means iterations of the build)"""
+        out = (ctypes.c_int64 * 3)()
+        check(lib().ia_ann_stats(self._h, out), 'ia_ann_stats')
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def build_ms(self):
+        """ia_ann_build_ms: host-clock ms of the build's (assign, grouping, update, list-major copy)"""
+        out = (ctypes.c_double * 4)()
+        check(lib().ia_ann_build_ms(self._h, out), 'ia_ann_build_ms')
+        return tuple(float(v) for v in out)
+
+    def close(self):
+        if self._h:
+            lib().ia_ann_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

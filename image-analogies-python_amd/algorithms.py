@@ -85,23 +85,41 @@ class GpuFLANN(object):
     params dict with 'checks'; nn_index(q, 1, checks=...) returns (indices, squared distances),
     1-D for num_neighbors = 1 and (nq, k) for k = 2..min(n, 64), nearest first; nn_radius(q, radius)
     returns the rows inside a squared radius of one query.
-    Backed by libia's exact GPU index; `algorithm` / `checks` are accepted and recorded."""
+    Backed by libia's exact GPU index; `algorithm` / `checks` are accepted and recorded.
+    algorithm='kmeans' (with iterations=5, n_lists=None, checks=32) instead builds the approximate index
+    (_native.AnnIndex), the one setting where nn_index's `checks` bounds the rows looked
+    at (default: the checks of the build; -1: every row, the exact answer); kmeans() returns that rule's centres."""
 
     def __init__(self, ctx=None):
         self._ctx = ctx
         self._index = None
+        self._ann = None      # the approximate index of algorithm='kmeans' (then _index is None)
+        self._checks = 32
 
     def build_index(self, pts, algorithm='kdtree', **kwargs):
-        self._index = _native.ExactIndex(self._ctx or default_context(), pts)
+        # the new index is built first: a build that raises leaves the previous index in place, as before
+        if algorithm == 'kmeans':
+            iters, checks = int(kwargs.get('iterations', 5)), int(kwargs.get('checks', 32))
+            ann = _native.AnnIndex(self._ctx or default_context(), pts, kwargs.get('n_lists'), iters)
+            self.delete_index()
+            self._ann, self._checks = ann, checks
+            return {'algorithm': 'kmeans', 'checks': checks, 'n_lists': ann.n_lists, 'iterations': iters,
+                    'exact': False}
+        index = _native.ExactIndex(self._ctx or default_context(), pts)
+        self.delete_index()
+        self._index = index
         params = {'algorithm': algorithm, 'checks': kwargs.get('checks', 32), 'exact': True}
         return params
 
     def nn_index(self, qpts, num_neighbors=1, checks=None, **kwargs):
-        if self._index is None:
+        if self._index is None and self._ann is None:
             raise _native.IAError('nn_index called before build_index')
-        kmax = min(self._index.n, _native.KNN_MAX)
+        kmax = min((self._index or self._ann).n, _native.KNN_MAX)
         if not 1 <= num_neighbors <= kmax:
             raise _native.IAError('GpuFLANN.nn_index: num_neighbors must be 1..%d (got %r)' % (kmax, num_neighbors))
+        if self._ann is not None:
+            idx, dist = self._ann.query(np.atleast_2d(qpts), num_neighbors, self._checks if checks is None else checks)
+            return (idx[:, 0], dist[:, 0]) if num_neighbors == 1 else (idx, dist)
         if num_neighbors == 1:
             return self._index.query(np.atleast_2d(qpts))
         return self._index.query_knn(np.atleast_2d(qpts), num_neighbors)   # (nq, k) arrays, as pyflann
@@ -111,6 +129,8 @@ class GpuFLANN(object):
         (strictly: dist < radius), nearest first, as (indices int64, squared distances float64);
         max_nn < 0: all of them, else the max_nn nearest.  sorted= / checks= are accepted and ignored
         (the result is always sorted and exact)."""
+        if self._ann is not None:
+            raise _native.IAError("GpuFLANN.nn_radius needs an exact index: build_index(pts, algorithm='linear')")
         if self._index is None:
             raise _native.IAError('nn_radius called before build_index')
         q = np.asarray(query, dtype=np.float64)
@@ -126,10 +146,20 @@ class GpuFLANN(object):
         cnt = min(int(count[0]), int(max_nn))
         return idx[0, :cnt].copy(), dist[0, :cnt].copy()
 
+    def kmeans(self, pts, num_clusters, max_iterations=None, dtype=None, **kwargs):
+        """pyflann's kmeans as a FLAT k-means (_native.kmeans): the (num_clusters, d) centres after at most
+        max_iterations rounds (None: 5); `branching` and pyflann's other keywords are accepted and ignored."""
+        centers = _native.kmeans(self._ctx or default_context(), pts, num_clusters,
+                                 5 if max_iterations is None else max_iterations)[0]
+        return centers if dtype is None else centers.astype(dtype)
+
     def delete_index(self):
         if self._index is not None:
             self._index.close()
             self._index = None
+        if self._ann is not None:
+            self._ann.close()
+            self._ann = None
 
 
 class IndexedRows(np.ndarray):

@@ -1,6 +1,6 @@
 // ia_launch.h — host launchers of the kernels in ia_level_db.hip, ia_gather.hip, ia_k3.hip,
 // ia_kernels.hip (the per-step merges), ia_merge_shard.hip, ia_dense.hip, ia_k3r.hip, ia_prune.hip,
-// ia_kcoh.hip, ia_nbhd.hip, ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
+// ia_kcoh.hip, ia_nbhd.hip, ia_ann.hip, ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
 // ia_k3.hip and ia_k3r.hip scan with one body (ia_k3_scan.h): ia_launch_k3, ia_launch_k3r_count and
 // ia_launch_k3r_fill take the same geometry (n_tiles, tpw, nwg; qt <= ia_k3_qtmax(KH) tiles from qt0).
 #pragma once
@@ -62,6 +62,15 @@ int ia_k3r_sort_lds();  // longest segment k3r_finish sorts in LDS
 void ia_launch_coherence_batch(const double *pts, int64_t n, int d, const double *q, int64_t nq, const int32_t *px,
                                const int32_t *s, const int32_t *im, int64_t n_s, int a_h, int a_w, int bp_w, int pad,
                                int32_t *p_out, int32_t *img_out, int32_t *r_out, unsigned *err, hipStream_t st);
+// the approximate index (ia_ann.hip; sequence in ia_ann.cpp).  rows / off: the lists (row indices list
+// after list, L + 1 offsets); centT: the centres transposed, d x L
+void ia_launch_ann_assign(const double *pts, int64_t n, int d, const double *cent, int L, int32_t *assign, hipStream_t st);
+void ia_launch_ann_update(const double *pts, int d, const int32_t *rows, const int32_t *off, int L, double *cent,
+                          hipStream_t st);
+void ia_launch_ann_permute(const double *pts, int d, const int32_t *rows, int64_t n, double *out, hipStream_t st);
+void ia_launch_ann_query(const double *rows, const int32_t *ids, const int32_t *off, const double *centT, int L, int d,
+                         const double *q, int nq, int k, int need, int64_t *idx, double *dist, unsigned long long *counters,
+                         hipStream_t st);
 // split-f16 matcher (IA_MATCH_F16X3)
 int ia_ks_for(int ch);
 double ia_k3h_tile_bytes(int KS);  // HBM bytes of one split-f16 DB tile (TileFmt)

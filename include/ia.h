@@ -441,6 +441,43 @@ int ia_coherence_batch(ia_index *index, const double *q, int64_t nq, const int32
                        const int32_t *s, const int32_t *im, int64_t n_s, int a_h, int a_w,
                        int bp_w, int pad, int32_t *p_out, int32_t *img_out, int32_t *rstar_out);
 
+/* ---- approximate index: k-means lists that honour `checks` ------------------ */
+/* A deterministic inverted file.  dist(a, b) is ia_index_*'s exact distance (fp64, numpy's pairwise
+ * order).  k-means over n rows of width d with L lists: centre c starts as row floor(c n / L);
+ * assign gives every row the centre of smallest (dist, centre index); update makes a centre the
+ * sum of its rows, added one by one in ascending row order, over their count (a centre without
+ * rows keeps its value); at most `iters` rounds of assign + update, stopping early when an
+ * assignment repeats; a last assign, so the lists always belong to the returned centres.  List c =
+ * the rows assigned to c in ascending row order (it may be empty).
+ * A query orders the centres by ascending (dist(centre, q), centre index) and takes lists whole, in
+ * that order, while fewer than `need` rows are taken: need = n for checks = -1, else
+ * min(n, max(checks, k)).  The answer is the k taken rows of smallest (dist, row index), ascending
+ * (ia_index_query_knn's order); checks = -1 or >= n is ia_index_query_knn's result bit for bit.
+ * Limits: 1 <= n_lists <= min(n, IA_ANN_MAX_LISTS), d <= 167, 1 <= k <= min(n, IA_KNN_MAX),
+ * checks = -1 or >= 1, iters >= 0, n < 2^31, every row and query value finite and at most
+ * IA_ANN_MAX_ABS = 2^500 in magnitude (no squared distance overflows).  Anything else is IA_EINVAL before
+ * any GPU call with nothing written; nq = 0 is IA_OK.  Not FLANN's randomised trees, and not the
+ * reference's result: an opt-in mode. */
+#define IA_ANN_MAX_LISTS 4096
+#define IA_ANN_MAX_ABS 0x1p500
+typedef struct ia_ann ia_ann;
+/* Lloyd's k-means by the rule above.  centers_out: k x d fp64; assign_out: n int32 (may be NULL);
+ * iters_run: the updates made (may be NULL).  Host memory. */
+int ia_kmeans(ia_ctx *ctx, const double *pts, int64_t n, int d, int k, int iters,
+              double *centers_out, int32_t *assign_out, int *iters_run);
+int ia_ann_build(ia_ctx *ctx, const double *pts, int64_t n, int d, int n_lists, int iters, ia_ann **out);
+/* centers_out L x d, sizes_out L int64, rows_out n int32 (list after list, each ascending); any may be NULL */
+int ia_ann_lists(const ia_ann *a, double *centers_out, int64_t *sizes_out, int32_t *rows_out);
+/* idx_out nq x k int64, dist_out nq x k fp64 (may be NULL) */
+int ia_ann_query(ia_ann *a, const double *q, int64_t nq, int k, int checks, int64_t *idx_out, double *dist_out);
+/* of the last ia_ann_query on this index, summed over its queries: rows whose distance was computed,
+ * lists probed (empty ones included); and the k-means iterations of the build */
+int ia_ann_stats(const ia_ann *a, int64_t out[3]);
+/* host-clock milliseconds of the build's phases, summed over its iterations: assign (with the
+ * read-back), grouping (host counting sort and upload), update, the list-major copy */
+int ia_ann_build_ms(const ia_ann *a, double out[4]);
+void ia_ann_destroy(ia_ann *a);
+
 /* ---- GPU preprocessing (img_setup, image_analogies.py:17-94) -------------------- */
 /* n_reduce steps of skimage 0.18.3 pyramid_reduce (img_preprocess.py:47-63): scipy.ndimage
  * gaussian_filter (sigma 2/3, mode 'reflect', 7 taps: weights7 = scipy's kernel, symmetric;
