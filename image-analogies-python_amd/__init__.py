@@ -13,3 +13,4 @@ __version__ = '0.1.0'
 
 from .img_preprocess import augment_pairs  # noqa: E402,F401  (ia_amd.augment_pairs)
 from .algorithms import build_similarity   # noqa: E402,F401  (ia_amd.build_similarity)
+from .image_analogies import mask_pyramid, resynthesize_pyramid  # noqa: E402,F401  (masked resynthesis)

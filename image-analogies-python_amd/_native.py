@@ -103,6 +103,13 @@ EXPORTS = {
                                                  ctypes.c_int, ctypes.POINTER(Stats)]),
     'ia_synthesize_levels_nbhd': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LevelArgs), ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, ctypes.POINTER(Stats)]),
+    'ia_synthesize_levels_masked': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LevelArgs), ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                                   ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                                   ctypes.POINTER(Stats)]),
+    'ia_masked_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
+    'ia_masked_step_list': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
     'ia_pipeline_depend': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     'ia_pipeline_generation': (ctypes.c_int, [ctypes.c_void_p]),
     'ia_synthesize_level': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LevelArgs), ctypes.POINTER(Stats)]),
@@ -262,6 +269,27 @@ def check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w, windows=(3, 5)):
                       % (feature_width(windows[0], windows[1], ch), windows[0], windows[0], windows[1], windows[1], ch,
                          w.shape))
     return ch
+
+
+def check_mask_state(B, mask, s, im):
+    """The mask and the kept state of a masked level call, as the C ABI reads them (include/ia.h
+    ia_synthesize_levels_masked): mask (b_h, b_w) bool or uint8, s (N, 2) and im (N,) integers, N = b_h b_w;
+    s = im = None: no kept pixel has a source (im = -1).  A mismatch raises instead of reading past a buffer.
+    Returns (mask uint8, s int32 (N, 2), im int32 (N,)), each a fresh C-contiguous array."""
+    bh, bw = B.shape[:2]
+    n = bh * bw
+    mask = np.asarray(mask)
+    if mask.shape != (bh, bw) or mask.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+        raise IAError('mask must be a bool or uint8 array of B\'s shape %s (got %s %s)' % ((bh, bw), mask.dtype, mask.shape))
+    if (s is None) != (im is None):
+        raise IAError('s and im are given together or not at all')
+    if s is None:
+        return np.array(mask, dtype=np.uint8, order='C'), np.zeros((n, 2), dtype=np.int32), np.full(n, -1, dtype=np.int32)
+    s, im = np.asarray(s), np.asarray(im)
+    if s.shape != (n, 2) or im.shape != (n,) or s.dtype.kind != 'i' or im.dtype.kind != 'i':
+        raise IAError('s must be (%d, 2) and im (%d,) integer arrays (got %s %s, %s %s)'
+                      % (n, n, s.dtype, s.shape, im.dtype, im.shape))
+    return np.array(mask, dtype=np.uint8, order='C'), np.array(s, dtype=np.int32, order='C'), np.array(im, dtype=np.int32, order='C')
 
 
 class Context(object):
@@ -487,6 +515,74 @@ class Context(object):
             check(lib().ia_synthesize_levels_kcoh(self._h, arr, len(args), None if sim is None else ctypes.c_void_p(int(sim)),
                                                   int(sim_k), ctypes.byref(st)), 'ia_synthesize_levels_kcoh')
         return st
+
+    def resynthesize_levels(self, A, Ac, Ap_list, Apc_list, jobs, windows=(3, 5), stats=None):
+        """ia_synthesize_levels_masked on host arrays: redo the masked pixels of one level
+        of several jobs that share the A side, and keep the rest exactly.  jobs: dicts as in synthesize_levels
+        (B, Bc, Bpc, Bp, weights, kappa_factor) plus mask (bool or uint8, b_h x b_w: True = redo) and s, im:
+        the previous state ((N, 2) and (N,); im < 0 = a kept pixel without a source; both None = none has
+        one).  Bp holds the kept values and is updated in place at the masked pixels only.  windows: (n_sm,
+        n_lg) for every job.  Returns [(s, im)]: the complete new maps (fresh arrays; the inputs are not
+        written)."""
+        windows = (int(windows[0]), int(windows[1]))
+        if not 1 <= len(jobs) <= 32:
+            raise IAError('resynthesize_levels: 1..32 jobs per call (got %d)' % len(jobs))
+        Ap = _c64(np.stack(Ap_list))
+        Apc = _c64(np.stack(Apc_list))
+        n_a = 0
+        if is_pair_list(A) or is_pair_list(Ac):
+            A_all, Ac_all = stack_pairs(A, Ac, Ap.shape[0])
+            A, Ac, n_a = A_all[0], Ac_all[0], Ap.shape[0]
+        else:
+            A, Ac = _c64(A), _c64(Ac)
+            A_all, Ac_all = A, Ac
+        keep, args, outs = [], [], []
+        for jb in jobs:
+            B, Bc, Bpc, Bp, w = _c64(jb['B']), _c64(jb['Bc']), _c64(jb['Bpc']), jb['Bp'], _c64(jb['weights'])
+            if not (isinstance(Bp, np.ndarray) and Bp.dtype == np.float64 and Bp.flags.c_contiguous):
+                raise IAError('Bp must be a C-contiguous float64 array (updated in place)')
+            ch = check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w, windows=windows)
+            mask, s, im = check_mask_state(B, jb['mask'], jb.get('s'), jb.get('im'))   # s / im: in and out (they may alias)
+            bh, bw = B.shape[:2]
+            args.append(LevelArgs(ch, Ap.shape[0], A.shape[0], A.shape[1], bh, bw,
+                                  _ptr(A_all), _ptr(Ac_all), _ptr(Ap), _ptr(Apc), _ptr(B), _ptr(Bc), _ptr(Bpc), _ptr(Bp),
+                                  _ptr(w), float(jb['kappa_factor']), _ptr(s), _ptr(im), IA_MEM_HOST, None, None, n_a))
+            keep.append((B, Bc, Bpc, w, mask))
+            outs.append((s, im))
+        n = len(args)
+        arr = (LevelArgs * n)(*args)
+        pm = (ctypes.c_void_p * n)(*[k[4].ctypes.data for k in keep])
+        ps = (ctypes.c_void_p * n)(*[o[0].ctypes.data for o in outs])
+        pi = (ctypes.c_void_p * n)(*[o[1].ctypes.data for o in outs])
+        st = stats if stats is not None else Stats()
+        check(lib().ia_synthesize_levels_masked(self._h, arr, n, windows[0], windows[1], pm, ps, pi, ctypes.byref(st)),
+              'ia_synthesize_levels_masked')
+        return outs
+
+    def resynthesize_levels_device(self, ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, windows=(3, 5), stats=None, n_a=0):
+        """ia_synthesize_levels_masked on device pointers: one ptrs dict per job as in synthesize_levels_device,
+        plus 'mask' (N bytes), 's_in' (N x 2 int32) and 'im_in' (N int32) addresses; s_in / im_in may equal
+        s_out / im_out."""
+        args = []
+        n_as = list(n_a) if isinstance(n_a, (list, tuple)) else [n_a] * len(ptr_list)
+        for ptrs, kf, na in zip(ptr_list, kappa_factors, n_as):
+            p = {k: ctypes.c_void_p(int(v)) for k, v in ptrs.items()}
+            args.append(LevelArgs(ch, n_ap, a_hw[0], a_hw[1], b_hw[0], b_hw[1], p['A'], p['Ac'], p['Ap'], p['Apc'],
+                                  p['B'], p['Bc'], p['Bpc'], p['Bp'], p['weights'], float(kf),
+                                  p['s_out'], p['im_out'], IA_MEM_DEVICE, None, None, int(na)))
+        n = len(args)
+        arr = (LevelArgs * n)(*args)
+        pm, ps, pi = ((ctypes.c_void_p * n)(*[int(p[k]) for p in ptr_list]) for k in ('mask', 's_in', 'im_in'))
+        st = stats if stats is not None else Stats()
+        check(lib().ia_synthesize_levels_masked(self._h, arr, n, int(windows[0]), int(windows[1]), pm, ps, pi,
+                                                ctypes.byref(st)), 'ia_synthesize_levels_masked')
+        return st
+
+    def masked_stats(self):
+        """ia_masked_stats: (levels (jobs) this context's masked calls ran, device ms of their step lists)"""
+        n, ms = ctypes.c_int64(), ctypes.c_double()
+        check(lib().ia_masked_stats(self._h, ctypes.byref(n), ctypes.byref(ms)), 'ia_masked_stats')
+        return n.value, ms.value
 
 
 KNN_MAX = 64  # IA_KNN_MAX of include/ia.h
@@ -749,6 +845,19 @@ def wavefront_step_pad(h, w, pad, t):
     r0, m = ctypes.c_int(), ctypes.c_int()
     check(lib().ia_wavefront_step_pad(h, w, pad, t, ctypes.byref(r0), ctypes.byref(m)), 'ia_wavefront_step_pad')
     return r0.value, m.value
+
+
+def masked_step_list(mask, pad):
+    """ia_masked_step_list: (offsets (T + 1,), pixels (count,)) int32 for a 2-D bool / uint8 mask: the masked
+    raster indices of step t of the schedule t = col + (pad + 1) row are pixels[offsets[t]:offsets[t + 1]]."""
+    mask = np.array(mask, dtype=np.uint8, order='C')
+    if mask.ndim != 2:
+        raise IAError('masked_step_list: a 2-D mask expected')
+    h, w = mask.shape
+    offsets = np.zeros(max(w + (pad + 1) * (h - 1), 0) + 1, dtype=np.int32)
+    pixels = np.zeros(max(int(np.count_nonzero(mask)), 1), dtype=np.int32)
+    check(lib().ia_masked_step_list(h, w, int(pad), _ptr(mask), _ptr(offsets), _ptr(pixels)), 'ia_masked_step_list')
+    return offsets, pixels[:int(offsets[-1])]
 
 
 def shard_tiles(n_rows, world, rank):

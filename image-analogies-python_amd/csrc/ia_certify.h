@@ -127,10 +127,13 @@ __device__ Winner certified_winner(const MergeArgs &a, int m, DistFn &&dist, uns
 
 // The rows a finish reads, as a policy R: row(i) where row i starts, dist(i, q) its exact unweighted
 // distance, len() the kappa dot's length (a constant or an int), pad() the window's p_l (Pad2 or an
-// int), ch() the channels.  LevelRows: a level's fp64 DB (K1b) under the default windows; the
-// window call brings its own (ia_nbhd.hip NbhdRows).
+// int), ch() the channels; kept: the level holds pixels without a source (im < 0: the masked call's
+// kept pixels of unknown origin), which are no coherence candidates.  LevelRows: a
+// level's fp64 DB (K1b) under the default windows; the window calls bring their own (ia_nbhd.h
+// NbhdRows).
 template <int CH>
 struct LevelRows {
+  static constexpr bool kept = false;
   const double *__restrict__ db64;
   __device__ __forceinline__ const double *row(int64_t i) const { return db64 + i * Geo<CH>::DS; }
   __device__ __forceinline__ double dist(int64_t i, const double *q) const { return exact_dist_level<CH>(db64, i, q); }
@@ -142,7 +145,8 @@ struct LevelRows {
 // best_coherence_match's pick for query pixel (r, c) (algorithms.py:92-130): candidates in
 // product(rows, cols) order (lane = window cell), first argmin of the correctly rounded sqrt of the
 // pairwise sum.  Independent of the NN winner, so the exchange merge runs it while the peers'
-// winners are in flight.  Every cell read is raster-earlier, hence of an earlier step.
+// winners are in flight.  Every cell read is raster-earlier, hence of an earlier step.  Under a
+// policy with `kept` a cell whose im is negative has no source: it is skipped and its s never read.
 struct CohPick {
   int pr, pc, img;
   bool has;
@@ -160,7 +164,9 @@ __device__ __forceinline__ CohPick coherence_pick(const Rows &R, const LevelGeo 
   int cpr = -1, cpc = -1, cim = 0;
   if (lane < causal_cells(R.pad())) {
     const auto n = causal_cell(R.pad(), g.bw, r, c, qi, lane);
-    if (n.ok) {
+    bool live = n.ok;
+    if constexpr (Rows::kept) live = n.ok && im[n.nb] >= 0;
+    if (live) {
       const ShiftedSrc t = shifted_src(g.ah, g.aw, s[2 * n.nb], s[2 * n.nb + 1], r, c, n.nr, n.nc);
       if (t.ok) {
         cim = im[n.nb];

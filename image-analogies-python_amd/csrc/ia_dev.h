@@ -21,6 +21,7 @@
 //                       sort (ia_index_*_radius)
 //   ia_kcoh.hip         k-coherence levels: a step without a DB scan (ia_synthesize_levels_kcoh)
 //   ia_nbhd.hip         exact levels for run-time window sizes (ia_synthesize_levels_nbhd)
+//   ia_mask.hip         masked resynthesis: step lists and list-driven steps (ia_synthesize_levels_masked)
 //   ia_ann.hip          the approximate index: k-means lists whose queries honour checks (ia_ann_*)
 //
 // The per-pixel window rule lives here, once, for all of them: win_feat (feature f of a pixel),

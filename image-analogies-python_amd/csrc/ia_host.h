@@ -126,6 +126,9 @@ struct __attribute__((visibility("hidden"))) ia_ctx {
   DevBuf tnorm;  // per DB tile of a pruned level: R_t >= max |a'| over its rows
   DevBuf sim;    // k-coherence levels (ia_synthesize_levels_kcoh): the similarity sets of a host-memory call,
   DevBuf kc_part, kc_cnt;  // ... and their scan waves' minima and counts (ia_kcoh.hip KcohScan)
+  DevBuf mk_mask, mk_off, mk_list;  // masked resynthesis (ia_synthesize_levels_masked): the jobs' masks, the step offsets and lists
+  int64_t mk_levels = 0;            // ... and its totals (ia_masked_stats): levels run, device ms of their lists
+  double mk_list_ms = 0.;
   DevBuf py_in, py_tmp, py_sm, py_mm, py_out;  // GPU preprocessing (ia_gaussian_pyramid, ia_color_matrix)
   std::vector<double> basis_h;   // staging of the basis upload (lives until the copy ran)
   int64_t prune_min_rows = IA_PRUNE_MIN_ROWS;  // option "prune_min_rows": smallest DB that prunes

@@ -1,6 +1,6 @@
 // ia_launch.h — host launchers of the kernels in ia_level_db.hip, ia_gather.hip, ia_k3.hip,
 // ia_kernels.hip (the per-step merges), ia_merge_shard.hip, ia_dense.hip, ia_k3r.hip, ia_prune.hip,
-// ia_kcoh.hip, ia_nbhd.hip, ia_ann.hip, ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
+// ia_kcoh.hip, ia_nbhd.hip, ia_mask.hip, ia_ann.hip, ia_pyramid.hip and ia_k3h.hip (the latter in ia_k3p_launch.hip); used by the host units (ia_host.h).
 // ia_k3.hip and ia_k3r.hip scan with one body (ia_k3_scan.h): ia_launch_k3, ia_launch_k3r_count and
 // ia_launch_k3r_fill take the same geometry (n_tiles, tpw, nwg; qt <= ia_k3_qtmax(KH) tiles from qt0).
 #pragma once
@@ -158,6 +158,21 @@ void ia_launch_nbhd_rows(const NbhdGeo &w, const Imgs &A, const APairs &ap, int6
 // coherence pick, kappa rule and writeback from the certified winners idx[m]
 void ia_launch_nbhd_gather(const NbhdGeo &w, const StepDesc &sd, const Imgs &B, const JobSet &jobs, double *q, hipStream_t st);
 void ia_launch_nbhd_finish(const NbhdGeo &w, const LevelGeo &g, const StepDesc &sd, const Imgs &A, const JobSet &jobs,
+                           const double *rows, const double *q, const int64_t *idx, hipStream_t st);
+// masked resynthesis (ia_mask.hip; include/ia.h ia_synthesize_levels_masked).  The pre-pass sets *err when a
+// pixel's im >= n_ap, or im >= 0 with s outside A.  mask: J x NB bytes, job-major.  count: offsets[t] = where
+// step t's entries start among all T steps' (offsets[T] = the total), entries in (job, row) ascending
+// order; fill: list[offsets[t] ..] = step t's (job, raster index).  gather / finish: ia_launch_nbhd_*'s
+// work for the n queries of one step's list
+void ia_launch_mask_check(const int32_t *s, const int32_t *im, int64_t NB, int n_ap, int ah, int aw, unsigned *err,
+                          hipStream_t st);
+void ia_launch_mask_count(const uint8_t *mask, int64_t NB, int J, int bh, int bw, int pad, int T, int32_t *offsets,
+                          hipStream_t st);
+void ia_launch_mask_fill(const uint8_t *mask, int64_t NB, int J, int bh, int bw, int pad, int T, int32_t *offsets, int2 *list,
+                         hipStream_t st);
+void ia_launch_mask_gather(const NbhdGeo &w, const Imgs &B, const JobSet &jobs, const int2 *list, int n, double *q,
+                           hipStream_t st);
+void ia_launch_mask_finish(const NbhdGeo &w, const LevelGeo &g, const Imgs &A, const JobSet &jobs, const int2 *list, int n,
                            const double *rows, const double *q, const int64_t *idx, hipStream_t st);
 // GPU preprocessing (ia_pyramid.hip)
 void ia_launch_pyramid_reduce(const double *in, double *out, double *tmp, double *sm, double *mm, int h, int w, int ch,

@@ -2,7 +2,7 @@
 // plan, the staged inputs, a step's descriptor, the stamp slots, the scan tally and the link
 // between pipelined levels, and the phase functions that ia_level_plan.cpp, ia_level_stats.cpp
 // and ia_level_kcoh.cpp define for the level call in ia_level_run.cpp (its steps: ia_level_run.h), and
-// what ia_level_nbhd.cpp's call (other window sizes) takes from them.
+// what ia_level_nbhd.cpp's call (other window sizes) and ia_level_mask.cpp's (masked resynthesis) take from them.
 #pragma once
 #include <chrono>
 #include <thread>
@@ -259,7 +259,11 @@ int run_kcoh_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInpu
 
 // levels of other window sizes (ia_level_nbhd.cpp): what the sizes, the context and
 // the batch must be for one, and the level after plan_shards and stage_level (P.g.D = w.D)
-int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg);
+// (who: the entry point the refusals name)
+int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg, const std::string &who = "ia_synthesize_levels_nbhd");
 int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const NbhdGeo &w, ia_stats *stats);
+// that call's DB between lv0 and lv1 (fp64 rows, finite check, fp32 tiles; *sc: their prescale), which the
+// masked call (ia_level_mask.cpp) builds too
+int build_nbhd_db(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, const NbhdGeo &w, const std::string &who, double *sc);
 
 }  // namespace ia_host

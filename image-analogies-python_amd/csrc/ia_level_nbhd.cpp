@@ -10,7 +10,7 @@
 
 namespace ia_host {
 
-int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg) {
+int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg, const std::string &who) {
   const bool dep = c->dep != nullptr;
   c->dep = nullptr;  // one level call per ia_pipeline_depend, refused or not
   c->dep_gen = 0;
@@ -18,16 +18,16 @@ int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg) 
   const NbhdGeo w = ia_nbhd_geo(ch, n_sm, n_lg);
   const bool sizes = (n_sm == 1 || n_sm == 3 || n_sm == 5) && (n_lg == 3 || n_lg == 5 || n_lg == 7 || n_lg == 9);
   if (!sizes || w.D > IA_MAX_D - 1)
-    return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: n_sm = " + std::to_string(n_sm) + ", n_lg = " + std::to_string(n_lg) +
+    return fail(IA_EINVAL, who + ": n_sm = " + std::to_string(n_sm) + ", n_lg = " + std::to_string(n_lg) +
                                " at " + std::to_string(ch) + " channel(s)" +
                                (sizes ? " gives D = " + std::to_string(w.D) + " features" : std::string()) +
                                ": n_sm must be 1, 3 or 5, n_lg 3, 5, 7 or 9, and D = ch (2 n_sm^2 + n_lg^2 + n_lg^2 / 2) <= " +
                                std::to_string(IA_MAX_D - 1));
   if (c->world > 1 || c->shard_emulate > 1)
-    return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: does not run on a sharded or shard-emulating context");
-  if (c->p_record || dep) return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: levels of this call are not pipelined");
+    return fail(IA_EINVAL, who + ": does not run on a sharded or shard-emulating context");
+  if (c->p_record || dep) return fail(IA_EINVAL, who + ": levels of this call are not pipelined");
   for (int j = 0; j < J; j++)
-    if (args[j].dbg_src) return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: produces no debug records");
+    if (args[j].dbg_src) return fail(IA_EINVAL, who + ": produces no debug records");
   return IA_OK;
 }
 
@@ -50,32 +50,20 @@ static int accumulate_nbhd_stats(ia_ctx *c, const LevelPlan &P, int64_t scans, i
   return IA_OK;
 }
 
-// The level after its staging.  DB: the fp64 rows with their column statistics (one read-back: it
-// also finds a non-finite A side before any step runs), then the index's centred, prescaled fp32
-// tiles.  Step t, all jobs: gather the query rows, the index's query prep, its scan in blocks of
-// ia_k3_qtmax(KH) query tiles, its certified merge, then coherence / kappa / writeback: five
-// launches (more scans when the step is wider than one block), nothing fused, nothing pruned.
-int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const NbhdGeo &w, ia_stats *stats) {
+// The window calls' DB (this call's and the masked one's, ia_level_mask.cpp), bracketed by lv0 / lv1:
+// the fp64 rows with their column statistics (one read-back: it also finds a non-finite A side before
+// any step runs; who: the entry point the refusal names), then the index's centred, prescaled fp32
+// tiles.  *sc: their prescale.
+int build_nbhd_db(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, const NbhdGeo &w, const std::string &who, double *sc) {
   const LevelGeo &g = P.g;
   const int D = w.D, KH = g.KH;
   int rc;
-  ia_wavefront_shape_pad(g.bh, g.bw, w.p_l, &P.T, &P.Mmax);
-  P.Mtmax = P.Mmax * P.J;
-  P.Mpad_max = tile_pad(P.Mtmax);
-  int tpw, nwg;
-  dense_geometry(g.n_tiles, &tpw, &nwg);
-  if ((rc = stage_jobs(c, P, in)) || (rc = c->db64.ensure((size_t)g.NA * D * 8)) || (rc = c->mu.ensure((size_t)D * 8)) ||
-      (rc = c->absmax.ensure(4)) || (rc = c->Rbits.ensure(4)) || (rc = c->counters.ensure(5 * 8)) ||
-      (rc = c->db.ensure((size_t)g.n_tiles * IA_TILE * 2 * KH * 4)) || (rc = c->q64.ensure((size_t)P.Mtmax * D * 8)) ||
-      (rc = c->qn2.ensure((size_t)P.Mpad_max * 8)) || (rc = c->qf.ensure((size_t)P.Mpad_max * 2 * KH * 4)) ||
-      (rc = c->rec.ensure((size_t)P.Mtmax * nwg * 16)) || (rc = c->recT.ensure((size_t)P.Mtmax * nwg * 4)) ||
-      (rc = c->win.ensure((size_t)P.Mtmax * 8)) || (rc = c->allwin.ensure((size_t)P.Mtmax * 8)))
+  if ((rc = c->db64.ensure((size_t)g.NA * D * 8)) || (rc = c->mu.ensure((size_t)D * 8)) || (rc = c->absmax.ensure(4)) ||
+      (rc = c->Rbits.ensure(4)) || (rc = c->db.ensure((size_t)g.n_tiles * IA_TILE * 2 * KH * 4)))
     return rc;
-  double *rows = c->db64.as<double>(), *mu = c->mu.as<double>(), *q64 = c->q64.as<double>();
-  int64_t *idx = c->win.as<int64_t>();
+  double *rows = c->db64.as<double>(), *mu = c->mu.as<double>();
   HIP_TRY(hipMemsetAsync(c->absmax.p, 0, 4, c->st));
   HIP_TRY(hipMemsetAsync(c->Rbits.p, 0, 4, c->st));
-  HIP_TRY(hipMemsetAsync(c->counters.p, 0, 5 * 8, c->st));
   HIP_TRY(hipEventRecord(c->lv0, c->st));
   ia_launch_nbhd_rows(w, in.Aim, in.Apairs, g.NA, rows, mu, c->absmax.as<unsigned>(), c->st);
   HIP_TRY(hipGetLastError());
@@ -88,10 +76,36 @@ int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInpu
   std::memcpy(&amaxf, &abits, 4);
   bool finite = std::isfinite(amaxf);
   for (int f = 0; f < D; f++) finite = finite && std::isfinite(mu_h[f]);
-  if (!finite) return fail(IA_EINVAL, "ia_synthesize_levels_nbhd: the A side must be finite (and its column sums too)");
-  const double sc = dense_prescale(amaxf);
-  ia_launch_dense_db(KH, rows, g.NA, D, g.n_tiles, mu, sc, c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
+  if (!finite) return fail(IA_EINVAL, who + ": the A side must be finite (and its column sums too)");
+  *sc = dense_prescale(amaxf);
+  ia_launch_dense_db(KH, rows, g.NA, D, g.n_tiles, mu, *sc, c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
   HIP_TRY(hipEventRecord(c->lv1, c->st));
+  return IA_OK;
+}
+
+// The level after its staging: the DB above, then step t, all jobs: gather the query rows, the
+// index's query prep, its scan in blocks of ia_k3_qtmax(KH) query tiles, its certified merge, then
+// coherence / kappa / writeback: five launches (more scans when the step is wider than one block),
+// nothing fused, nothing pruned.
+int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const NbhdGeo &w, ia_stats *stats) {
+  const LevelGeo &g = P.g;
+  const int D = w.D, KH = g.KH;
+  int rc;
+  ia_wavefront_shape_pad(g.bh, g.bw, w.p_l, &P.T, &P.Mmax);
+  P.Mtmax = P.Mmax * P.J;
+  P.Mpad_max = tile_pad(P.Mtmax);
+  int tpw, nwg;
+  dense_geometry(g.n_tiles, &tpw, &nwg);
+  if ((rc = stage_jobs(c, P, in)) || (rc = c->counters.ensure(5 * 8)) || (rc = c->q64.ensure((size_t)P.Mtmax * D * 8)) ||
+      (rc = c->qn2.ensure((size_t)P.Mpad_max * 8)) || (rc = c->qf.ensure((size_t)P.Mpad_max * 2 * KH * 4)) ||
+      (rc = c->rec.ensure((size_t)P.Mtmax * nwg * 16)) || (rc = c->recT.ensure((size_t)P.Mtmax * nwg * 4)) ||
+      (rc = c->win.ensure((size_t)P.Mtmax * 8)) || (rc = c->allwin.ensure((size_t)P.Mtmax * 8)))
+    return rc;
+  HIP_TRY(hipMemsetAsync(c->counters.p, 0, 5 * 8, c->st));
+  double sc;
+  if ((rc = build_nbhd_db(c, P, in, w, "ia_synthesize_levels_nbhd", &sc))) return rc;
+  double *rows = c->db64.as<double>(), *mu = c->mu.as<double>(), *q64 = c->q64.as<double>();
+  int64_t *idx = c->win.as<int64_t>();
 
   const MergeArgs ma = dense_merge_args(c->rec.as<float4>(), c->recT.as<float>(), c->qn2.as<double>(), c->Rbits.as<unsigned>(),
                                         nwg, tpw, g.n_tiles, g.NA, KH);

@@ -9,13 +9,13 @@
 //   k_nbhd_gather    the fp64 query rows of one wavefront step, one wave per query, all jobs
 //   k_nbhd_finish    K4's finish_pixel (ia_certify.h) over this call's rows: best_coherence_match
 //                    over the (p_l + 1) x (2 p_l + 1) window, the kappa rule, the B' / s / im writeback
+//                    (both bodies in ia_nbhd.h, which the masked call's kernels share: ia_mask.hip)
 //
 // Between gather and finish a step runs the index's kernels unchanged: k_dense_query, k3_dist and
 // k_merge_dense (certified_winner over row_dist2_rt), so the NN is the exact fp64 one.
 // The per-pixel rules are the default path's own text, compiled here with run-time geometry:
 // win_feat, ia_qpix, causal_cell / shifted_src, blas_dot_sq and kappa_rule (ia_dev.h, ia_internal.h).
-#include "ia_certify.h"
-#include "ia_launch.h"
+#include "ia_nbhd.h"
 
 __global__ void __launch_bounds__(IA_WG) k_nbhd_rows(NbhdGeo w, Imgs A, APairs ap, int64_t NA, double *__restrict__ rows) {
   const int64_t n = NA * w.D, hw = (int64_t)A.h * A.w;
@@ -62,24 +62,10 @@ __global__ void __launch_bounds__(IA_WG) k_nbhd_colstats(const double *__restric
 
 template <class JS>
 __global__ void __launch_bounds__(IA_WG) k_nbhd_gather(NbhdGeo w, StepDesc sd, Imgs B, JS jobs, double *__restrict__ q) {
-  const int lane = threadIdx.x & 63;
   const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
   if (m >= sd.J * sd.M) return;
-  const QPix px = ia_qpix(sd, B.w, m, w.p_l + 1);
-  if constexpr (!JS::single) B = job_imgs(B, jobs.get(px.job));  // single job: B already holds its images
-  for (int f = lane; f < w.D; f += IA_WAVE) q[(int64_t)m * w.D + f] = win_feat(w, B, f, px.r, px.c, 0);
+  nbhd_gather_query(w, B, jobs, ia_qpix(sd, B.w, m, w.p_l + 1), m, q);
 }
-
-// this call's rows as finish_pixel reads them (ia_certify.h LevelRows): N_A x D contiguous
-struct NbhdRows {
-  const double *__restrict__ rows;
-  int D, p_l, nch;
-  __device__ __forceinline__ const double *row(int64_t i) const { return rows + i * D; }
-  __device__ __forceinline__ double dist(int64_t i, const double *q) const { return row_dist2_rt(row(i), q, D); }
-  __device__ __forceinline__ int len() const { return D; }
-  __device__ __forceinline__ int pad() const { return p_l; }
-  __device__ __forceinline__ int ch() const { return nch; }
-};
 
 template <class JS>
 __global__ void __launch_bounds__(IA_WG) k_nbhd_finish(NbhdGeo w, LevelGeo g, StepDesc sd, Imgs A, JS jobs,
@@ -87,12 +73,7 @@ __global__ void __launch_bounds__(IA_WG) k_nbhd_finish(NbhdGeo w, LevelGeo g, St
                                                        const int64_t *__restrict__ idx) {
   const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
   if (m >= sd.J * sd.M) return;
-  const QPix px = ia_qpix(sd, g.bw, m, w.p_l + 1);
-  const JobPtrs jp = jobs.get(px.job);
-  int64_t app_ix = idx[m];
-  if ((uint64_t)app_ix >= (uint64_t)g.NA) app_ix = 0;  // (no winner: a NaN query; never an index past the DB)
-  finish_pixel(NbhdRows{rows, w.D, w.p_l, w.ch}, g, A, px.r, px.c, app_ix, q64 + (int64_t)m * w.D, jp.s, jp.im, jp.Bp,
-               jp.weights, jp.kf, jp.pstat, 0u);
+  nbhd_finish_query<false>(w, g, A, jobs, ia_qpix(sd, g.bw, m, w.p_l + 1), m, rows, q64, idx);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -203,6 +203,70 @@ def synthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, c, ctx=None, stats=Non
     return S, IM
 
 
+def mask_pyramid(mask, shapes, grow=0):
+    """The masks of every level for a mask of the finest: shapes[l] = (h, w) of level l (coarsest first, as
+    the pyramids are).  The finest level is `mask`; level l - 1 at (r, c) is the `any` over the 2 x 2 block
+    (2r .. 2r + 1, 2c .. 2c + 1) of level l, clipped to that level.  grow = g dilates each level of that
+    chain by a (2g + 1)-pixel square (clipped at the borders), after the reduction: the reductions run on
+    the undilated masks.
+    grow is a quality choice, not a correctness one: a kept fine pixel next to a changed coarse pixel is not
+    re-decided, although its coarse window now reads new values; a larger grow re-decides a wider rim."""
+    L = len(shapes)
+    m = np.asarray(mask).astype(bool)
+    if m.shape != tuple(shapes[-1][:2]):
+        raise ValueError('mask must have the finest level\'s shape %r (got %r)' % (tuple(shapes[-1][:2]), m.shape))
+    chain = [None] * L
+    chain[L - 1] = m
+    for l in range(L - 1, 0, -1):
+        h, w = shapes[l - 1][:2]
+        if (h, w) != (-(-chain[l].shape[0] // 2), -(-chain[l].shape[1] // 2)):
+            raise ValueError('level %d must be the ceil half of level %d: %r vs %r' % (l - 1, l, (h, w), chain[l].shape))
+        p = np.zeros((2 * h, 2 * w), dtype=bool)
+        p[:chain[l].shape[0], :chain[l].shape[1]] = chain[l]
+        chain[l - 1] = p.reshape(h, 2, w, 2).any(axis=(1, 3))
+    g = int(grow)
+    if g <= 0:
+        return chain
+    out = []
+    for m in chain:
+        h, w = m.shape
+        p = np.zeros((h + 2 * g, w + 2 * g), dtype=bool)
+        p[g:g + h, g:g + w] = m
+        d = np.zeros((h, w), dtype=bool)
+        for dy in range(2 * g + 1):
+            for dx in range(2 * g + 1):
+                d |= p[dy:dy + h, dx:dx + w]
+        out.append(d)
+    return out
+
+
+def resynthesize_pyramid(A_pyr, Ap_pyr_list, B_pyr, Bp_pyr, S, IM, mask, c, ctx=None, stats=None, grow=0):
+    """Redo a region of a finished synthesis and keep the rest, exactly: levels
+    1..max_levels-1 through ia_synthesize_levels_masked with the masks mask_pyramid(mask, ., grow) and
+    level_windows(c) sizes.  Bp_pyr holds the previous result (or a B' known in part) and is updated in place
+    at the masked pixels only; S / IM are the previous {level: s} / {level: im} - a level that is missing or
+    None has no sources (im = -1: hole filling).  B_pyr is the (edited) B pyramid.  Returns the new (S, IM).
+    A region's bottom and right borders are not matched against the kept pixels beyond them."""
+    lv = Ap_pyr_list[0][-1]
+    windows = level_windows(c, ch=1 if lv.ndim == 2 else lv.shape[2])
+    if windows == (3, 5):
+        check_windows(c)
+    ctx = ctx or default_context()
+    L = c.max_levels
+    masks = mask_pyramid(mask, [x.shape[:2] for x in Bp_pyr[:L]], grow)
+    S, IM = S or {}, IM or {}
+    S_new, IM_new = {}, {}
+    stats = stats if stats is not None else _native.Stats()
+    for level in range(1, L):
+        Bp_pyr[level] = np.ascontiguousarray(Bp_pyr[level], dtype=np.float64)
+        job = dict(B=B_pyr[level], Bc=B_pyr[level - 1], Bpc=Bp_pyr[level - 1], Bp=Bp_pyr[level], weights=c.weights,
+                   kappa_factor=1 + (2 ** (level - L)) * c.k, mask=masks[level], s=S.get(level), im=IM.get(level))
+        S_new[level], IM_new[level] = ctx.resynthesize_levels(
+            a_levels(A_pyr, level), a_levels(A_pyr, level - 1), [p[level] for p in Ap_pyr_list],
+            [p[level - 1] for p in Ap_pyr_list], [job], windows=windows, stats=stats)[0]
+    return S_new, IM_new
+
+
 def level_colour(level, Bp_pyr, S, IM, color_pyr_list, c):
     """Colour output of a level (image_analogies.py:216-217, 255-258)."""
     if c.convert:

@@ -351,6 +351,41 @@ int ia_synthesize_levels_kcoh(ia_ctx *ctx, const ia_level_args *args, int n_jobs
 int ia_synthesize_levels_nbhd(ia_ctx *ctx, const ia_level_args *args, int n_jobs, int n_sm, int n_lg,
                               ia_stats *stats);
 
+/* Masked resynthesis: redo the pixels of a mask and keep the rest of the level, exactly.
+ * The jobs, sizes, batching and memory kinds are ia_synthesize_levels_nbhd's.  Per job j, in the memory
+ * kind args[0].mem names (the three pointer arrays themselves are host arrays of n_jobs entries):
+ *   mask[j]   N = b_h b_w bytes: nonzero = synthesise this pixel, zero = keep it;
+ *   s_in[j]   N x 2 int32, im_in[j] N int32: the state of the kept pixels.  im_in < 0: the kept pixel has
+ *             no source (a B' known in part, origin unknown): it is never a coherence candidate and its
+ *             s_in is not read;
+ *   args[j].Bp on entry: the complete B' level: the kept values, and anything at the masked pixels.
+ * The masked pixels are visited in raster order, each by ia_synthesize_levels_nbhd's per-pixel rule on the
+ * current state, with one change: a coherence cell is a candidate only if it is raster-earlier, its im >= 0
+ * and its shifted source lies inside A.  Kept pixels are never written: their Bp values and s / im entries
+ * come out bit-identical.  s_out / im_out are the complete maps (kept entries copied, masked entries
+ * new); s_in[j] may be args[j].s_out, im_in[j] may be args[j].im_out.  A raster-later pixel a masked pixel
+ * reads (through border reflection only: rows and columns below p_l) holds what Bp held on entry.
+ * The schedule is t = col + (p_l + 1) row restricted to the masked pixels; only steps that hold one run.
+ * An all-ones mask with every im_in = -1 is ia_synthesize_levels_nbhd bit for bit.  From the state a
+ * finished ia_synthesize_levels_nbhd run of the same inputs left, any mask inside rows >= p_l and columns
+ * >= p_l reproduces that state bit for bit.  A job whose mask is all zero is legal: its outputs are its
+ * inputs.  A region's bottom and right borders are not matched against the kept pixels beyond them (the
+ * window is causal), so seams there are possible.
+ * ia_stats: pixels += masked pixels, steps += steps that held one, dist_launches += scans launched;
+ * coherence_wins, kappa_ambiguous, db_ms and synth_ms as ia_synthesize_levels_nbhd; nbhd_levels is not
+ * touched (ia_masked_stats counts these levels).
+ * IA_EINVAL before any step runs and with nothing written: everything ia_synthesize_levels_nbhd refuses
+ * (the message names this call), a NULL mask / s_in / im_in or a NULL entry, a pixel with im_in >= n_ap,
+ * a pixel with im_in >= 0 whose s_in lies outside [0, a_h) x [0, a_w) (one pre-pass kernel over every
+ * pixel, masked ones included), n_jobs b_h b_w >= 2^31. */
+int ia_synthesize_levels_masked(ia_ctx *ctx, const ia_level_args *args, int n_jobs, int n_sm, int n_lg,
+                                const uint8_t *const *mask, const int32_t *const *s_in,
+                                const int32_t *const *im_in, ia_stats *stats);
+/* Totals of the context's ia_synthesize_levels_masked calls since ia_init: *levels = levels (jobs) run,
+ * *list_ms = device time of their step lists (count, scan and fill passes).  Either may be NULL.
+ * (ia_stats keeps its layout: these counters travel on their own.) */
+int ia_masked_stats(ia_ctx *ctx, int64_t *levels, double *list_ms);
+
 /* Level pipelining: level l + 1 of a job only reads B' of level l near
  * (r / 2, c / 2), so its wavefront step t needs level l's steps <= t / 2 + 4, not the whole level.
  * Two contexts driven from two host threads run alternate levels concurrently: the context of
@@ -527,6 +562,11 @@ int ia_wavefront_step(int h, int w, int64_t t, int *r0, int *M);
  * pad = 2 gives what ia_wavefront_shape / ia_wavefront_step give. */
 int ia_wavefront_shape_pad(int h, int w, int pad, int64_t *steps, int64_t *max_queries);
 int ia_wavefront_step_pad(int h, int w, int pad, int64_t t, int *r0, int *M);
+/* The compaction rule of ia_synthesize_levels_masked for one job: the masked pixels (mask: h w bytes,
+ * nonzero = masked) of every step of that schedule, T = w + (pad + 1)(h - 1) steps.  offsets has T + 1
+ * entries; pixels[offsets[t] .. offsets[t + 1]) are the masked raster indices of step t, rows ascending;
+ * offsets[T] = the mask's count, which pixels must hold (pixels = NULL: offsets only). */
+int ia_masked_step_list(int h, int w, int pad, const uint8_t *mask, int32_t *offsets, int32_t *pixels);
 /* DB tiles [tile0, tile1) owned by `rank` of `world` for a level of n_rows DB rows.  The DB is
  * stored in NT = ceil(n_rows/32) tiles of 32 positions; position j of tile t holds row
  * j*NT + (t * (2654435761 mod NT) mod NT) (tile-strided and tile-scattered, so neighbouring A
