@@ -292,6 +292,59 @@ def check_mask_state(B, mask, s, im):
     return np.array(mask, dtype=np.uint8, order='C'), np.array(s, dtype=np.int32, order='C'), np.array(im, dtype=np.int32, order='C')
 
 
+def _a_side(A, Ac, Ap_list, Apc_list):
+    """The A side of a host level call: (A, Ac, A_all, Ac_all, Ap, Apc, n_a).  A / Ac: one image, what the
+    shapes are checked on; A_all / Ac_all: what the library reads, (n_a, h, w[, ch]) when A or Ac is a list
+    with one image per A' (pairs; n_a = n_ap), else the one shared image (n_a = 0)."""
+    Ap = _c64(np.stack(Ap_list))
+    Apc = _c64(np.stack(Apc_list))
+    if is_pair_list(A) or is_pair_list(Ac):
+        A_all, Ac_all = stack_pairs(A, Ac, Ap.shape[0])
+        return A_all[0], Ac_all[0], A_all, Ac_all, Ap, Apc, Ap.shape[0]
+    A, Ac = _c64(A), _c64(Ac)
+    return A, Ac, A, Ac, Ap, Apc, 0
+
+
+def _host_job(a_side, jb, windows, masked):
+    """One job of a host level call: its arrays converted and checked against the A side, its maps s / im
+    (masked: the checked copies of the job's kept state, which the call updates; else fresh ones), its debug
+    records (a job with a debug dict, not masked) and its LevelArgs.  Returns (LevelArgs, the converted
+    arrays - the mask last - which the caller keeps alive through the call, s, im, dsrc, ddist)."""
+    A, Ac, A_all, Ac_all, Ap, Apc, n_a = a_side
+    B, Bc, Bpc, Bp, w = _c64(jb['B']), _c64(jb['Bc']), _c64(jb['Bpc']), jb['Bp'], _c64(jb['weights'])
+    if not (isinstance(Bp, np.ndarray) and Bp.dtype == np.float64 and Bp.flags.c_contiguous):
+        raise IAError('Bp must be a C-contiguous float64 array (updated in place)')
+    ch = check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w, windows=windows)
+    bh, bw = B.shape[:2]
+    kept, dsrc, ddist = (B, Bc, Bpc, w), None, None
+    if masked:
+        mask, s, im = check_mask_state(B, jb['mask'], jb.get('s'), jb.get('im'))   # s / im: in and out (they may alias)
+        kept += (mask,)
+    else:
+        s, im = np.empty((bh * bw, 2), dtype=np.int32), np.empty(bh * bw, dtype=np.int32)
+        if jb.get('debug') is not None:
+            dsrc = np.zeros((bh * bw, 6), dtype=np.int32)
+            ddist = np.zeros((bh * bw, 2), dtype=np.float64)
+    args = LevelArgs(ch, Ap.shape[0], A.shape[0], A.shape[1], bh, bw,
+                     _ptr(A_all), _ptr(Ac_all), _ptr(Ap), _ptr(Apc), _ptr(B), _ptr(Bc), _ptr(Bpc), _ptr(Bp),
+                     _ptr(w), float(jb['kappa_factor']), _ptr(s), _ptr(im), IA_MEM_HOST,
+                     None if dsrc is None else _ptr(dsrc), None if ddist is None else _ptr(ddist), n_a)
+    return args, kept, s, im, dsrc, ddist
+
+
+def _device_jobs(ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, n_a):
+    """The LevelArgs array of a device level call: one ptrs dict and kappa factor per job; n_a: one value for
+    all jobs or one per job."""
+    args = []
+    n_as = list(n_a) if isinstance(n_a, (list, tuple)) else [n_a] * len(ptr_list)
+    for ptrs, kf, na in zip(ptr_list, kappa_factors, n_as):
+        p = {k: ctypes.c_void_p(int(v)) for k, v in ptrs.items()}
+        args.append(LevelArgs(ch, n_ap, a_hw[0], a_hw[1], b_hw[0], b_hw[1], p['A'], p['Ac'], p['Ap'], p['Apc'],
+                              p['B'], p['Bc'], p['Bpc'], p['Bp'], p['weights'], float(kf),
+                              p['s_out'], p['im_out'], IA_MEM_DEVICE, None, None, int(na)))
+    return (LevelArgs * len(args))(*args)
+
+
 class Context(object):
     """One GPU (ia_ctx).  device: HIP ordinal (default: LOCAL_RANK or 0)."""
 
@@ -423,15 +476,8 @@ class Context(object):
                 raise IAError('synthesize_levels: windows= takes neither sim nor debug (ia_synthesize_levels_nbhd)')
         if not 1 <= len(jobs) <= 32:
             raise IAError('synthesize_levels: 1..32 jobs per call (got %d)' % len(jobs))
-        Ap = _c64(np.stack(Ap_list))
-        Apc = _c64(np.stack(Apc_list))
-        n_a = 0
-        if is_pair_list(A) or is_pair_list(Ac):
-            A_all, Ac_all = stack_pairs(A, Ac, Ap.shape[0])   # (n_a, h, w[, ch]): what the library reads
-            A, Ac, n_a = A_all[0], Ac_all[0], Ap.shape[0]     # one image: what the shapes are checked on
-        else:
-            A, Ac = _c64(A), _c64(Ac)
-            A_all, Ac_all = A, Ac
+        a_side = _a_side(A, Ac, Ap_list, Apc_list)
+        A, Ap = a_side[0], a_side[4]
         sim_k = 0
         if sim is not None:
             sim = np.ascontiguousarray(sim, dtype=np.int32)
@@ -440,22 +486,9 @@ class Context(object):
             sim_k = sim.shape[1]
         keep, args, outs = [], [], []
         for jb in jobs:
-            B, Bc, Bpc, Bp, w = _c64(jb['B']), _c64(jb['Bc']), _c64(jb['Bpc']), jb['Bp'], _c64(jb['weights'])
-            if not (isinstance(Bp, np.ndarray) and Bp.dtype == np.float64 and Bp.flags.c_contiguous):
-                raise IAError('Bp must be a C-contiguous float64 array (updated in place)')
-            ch = check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w, windows=windows or (3, 5))
-            bh, bw = B.shape[:2]
-            s = np.empty((bh * bw, 2), dtype=np.int32)
-            im = np.empty(bh * bw, dtype=np.int32)
-            dsrc = ddist = None
-            if jb.get('debug') is not None:
-                dsrc = np.zeros((bh * bw, 6), dtype=np.int32)
-                ddist = np.zeros((bh * bw, 2), dtype=np.float64)
-            args.append(LevelArgs(ch, Ap.shape[0], A.shape[0], A.shape[1], bh, bw,
-                                  _ptr(A_all), _ptr(Ac_all), _ptr(Ap), _ptr(Apc), _ptr(B), _ptr(Bc), _ptr(Bpc), _ptr(Bp),
-                                  _ptr(w), float(jb['kappa_factor']), _ptr(s), _ptr(im), IA_MEM_HOST,
-                                  None if dsrc is None else _ptr(dsrc), None if ddist is None else _ptr(ddist), n_a))
-            keep.append((B, Bc, Bpc, w))
+            a, kept, s, im, dsrc, ddist = _host_job(a_side, jb, windows or (3, 5), False)
+            args.append(a)
+            keep.append(kept)
             outs.append((s, im, dsrc, ddist, jb.get('debug')))
         arr = (LevelArgs * len(args))(*args)
         st = stats if stats is not None else Stats()
@@ -495,24 +528,17 @@ class Context(object):
         must be equal in all of them), one kappa factor per job; n_a as in synthesize_level_device,
         or a list with one value per job (the library refuses jobs that differ).  sim / sim_k: the A side's
         similarity sets on the device, for every job (synthesize_level_device)."""
-        args = []
-        n_as = list(n_a) if isinstance(n_a, (list, tuple)) else [n_a] * len(ptr_list)
-        for ptrs, kf, na in zip(ptr_list, kappa_factors, n_as):
-            p = {k: ctypes.c_void_p(int(v)) for k, v in ptrs.items()}
-            args.append(LevelArgs(ch, n_ap, a_hw[0], a_hw[1], b_hw[0], b_hw[1], p['A'], p['Ac'], p['Ap'], p['Apc'],
-                                  p['B'], p['Bc'], p['Bpc'], p['Bp'], p['weights'], float(kf),
-                                  p['s_out'], p['im_out'], IA_MEM_DEVICE, None, None, int(na)))
-        arr = (LevelArgs * len(args))(*args)
+        arr = _device_jobs(ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, n_a)
         st = stats if stats is not None else Stats()
         if windows is not None:
             if sim is not None or sim_k:
                 raise IAError('synthesize_levels_device: windows= takes no sim (ia_synthesize_levels_nbhd)')
-            check(lib().ia_synthesize_levels_nbhd(self._h, arr, len(args), int(windows[0]), int(windows[1]), ctypes.byref(st)),
+            check(lib().ia_synthesize_levels_nbhd(self._h, arr, len(arr), int(windows[0]), int(windows[1]), ctypes.byref(st)),
                   'ia_synthesize_levels_nbhd')
         elif sim is None and not sim_k:
-            check(lib().ia_synthesize_levels(self._h, arr, len(args), ctypes.byref(st)), 'ia_synthesize_levels')
+            check(lib().ia_synthesize_levels(self._h, arr, len(arr), ctypes.byref(st)), 'ia_synthesize_levels')
         else:
-            check(lib().ia_synthesize_levels_kcoh(self._h, arr, len(args), None if sim is None else ctypes.c_void_p(int(sim)),
+            check(lib().ia_synthesize_levels_kcoh(self._h, arr, len(arr), None if sim is None else ctypes.c_void_p(int(sim)),
                                                   int(sim_k), ctypes.byref(st)), 'ia_synthesize_levels_kcoh')
         return st
 
@@ -527,27 +553,12 @@ class Context(object):
         windows = (int(windows[0]), int(windows[1]))
         if not 1 <= len(jobs) <= 32:
             raise IAError('resynthesize_levels: 1..32 jobs per call (got %d)' % len(jobs))
-        Ap = _c64(np.stack(Ap_list))
-        Apc = _c64(np.stack(Apc_list))
-        n_a = 0
-        if is_pair_list(A) or is_pair_list(Ac):
-            A_all, Ac_all = stack_pairs(A, Ac, Ap.shape[0])
-            A, Ac, n_a = A_all[0], Ac_all[0], Ap.shape[0]
-        else:
-            A, Ac = _c64(A), _c64(Ac)
-            A_all, Ac_all = A, Ac
+        a_side = _a_side(A, Ac, Ap_list, Apc_list)
         keep, args, outs = [], [], []
         for jb in jobs:
-            B, Bc, Bpc, Bp, w = _c64(jb['B']), _c64(jb['Bc']), _c64(jb['Bpc']), jb['Bp'], _c64(jb['weights'])
-            if not (isinstance(Bp, np.ndarray) and Bp.dtype == np.float64 and Bp.flags.c_contiguous):
-                raise IAError('Bp must be a C-contiguous float64 array (updated in place)')
-            ch = check_level_shapes(A, Ac, Ap, Apc, B, Bc, Bpc, Bp, w, windows=windows)
-            mask, s, im = check_mask_state(B, jb['mask'], jb.get('s'), jb.get('im'))   # s / im: in and out (they may alias)
-            bh, bw = B.shape[:2]
-            args.append(LevelArgs(ch, Ap.shape[0], A.shape[0], A.shape[1], bh, bw,
-                                  _ptr(A_all), _ptr(Ac_all), _ptr(Ap), _ptr(Apc), _ptr(B), _ptr(Bc), _ptr(Bpc), _ptr(Bp),
-                                  _ptr(w), float(jb['kappa_factor']), _ptr(s), _ptr(im), IA_MEM_HOST, None, None, n_a))
-            keep.append((B, Bc, Bpc, w, mask))
+            a, kept, s, im, _, _ = _host_job(a_side, jb, windows, True)
+            args.append(a)
+            keep.append(kept)
             outs.append((s, im))
         n = len(args)
         arr = (LevelArgs * n)(*args)
@@ -563,15 +574,8 @@ class Context(object):
         """ia_synthesize_levels_masked on device pointers: one ptrs dict per job as in synthesize_levels_device,
         plus 'mask' (N bytes), 's_in' (N x 2 int32) and 'im_in' (N int32) addresses; s_in / im_in may equal
         s_out / im_out."""
-        args = []
-        n_as = list(n_a) if isinstance(n_a, (list, tuple)) else [n_a] * len(ptr_list)
-        for ptrs, kf, na in zip(ptr_list, kappa_factors, n_as):
-            p = {k: ctypes.c_void_p(int(v)) for k, v in ptrs.items()}
-            args.append(LevelArgs(ch, n_ap, a_hw[0], a_hw[1], b_hw[0], b_hw[1], p['A'], p['Ac'], p['Ap'], p['Apc'],
-                                  p['B'], p['Bc'], p['Bpc'], p['Bp'], p['weights'], float(kf),
-                                  p['s_out'], p['im_out'], IA_MEM_DEVICE, None, None, int(na)))
-        n = len(args)
-        arr = (LevelArgs * n)(*args)
+        arr = _device_jobs(ch, n_ap, a_hw, b_hw, ptr_list, kappa_factors, n_a)
+        n = len(arr)
         pm, ps, pi = ((ctypes.c_void_p * n)(*[int(p[k]) for p in ptr_list]) for k in ('mask', 's_in', 'im_in'))
         st = stats if stats is not None else Stats()
         check(lib().ia_synthesize_levels_masked(self._h, arr, n, int(windows[0]), int(windows[1]), pm, ps, pi,

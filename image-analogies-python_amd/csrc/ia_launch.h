@@ -154,26 +154,30 @@ inline NbhdGeo ia_nbhd_geo(int ch, int n_sm, int n_lg) {
 // the caller) = the bits of the largest centred |value| as a float, rounded up
 void ia_launch_nbhd_rows(const NbhdGeo &w, const Imgs &A, const APairs &ap, int64_t NA, double *rows, double *mu,
                          unsigned *amax_bits, hipStream_t st);
-// the step's query rows q[m, 0..D), m < sd.J sd.M (pixel (r, sd.t - (p_l + 1) r)), and its pixels'
-// coherence pick, kappa rule and writeback from the certified winners idx[m]
-void ia_launch_nbhd_gather(const NbhdGeo &w, const StepDesc &sd, const Imgs &B, const JobSet &jobs, double *q, hipStream_t st);
-void ia_launch_nbhd_finish(const NbhdGeo &w, const LevelGeo &g, const StepDesc &sd, const Imgs &A, const JobSet &jobs,
+// One step of a window level, from either window call: n queries, the wavefront step sd's (list =
+// nullptr; n = sd.J sd.M, query m at pixel (r, sd.t - (p_l + 1) r)) or the entries list[0..n) of a
+// masked step's list (job, raster index; sd unused).
+struct NbhdStep {
+  StepDesc sd;
+  const int2 *list;
+  int n;
+};
+// the step's query rows q[m, 0..D), m < n, and its pixels' coherence pick, kappa rule and writeback
+// from the certified winners idx[m] (a listed step's pick skips cells without a source)
+void ia_launch_nbhd_gather(const NbhdGeo &w, const NbhdStep &step, const Imgs &B, const JobSet &jobs, double *q, hipStream_t st);
+void ia_launch_nbhd_finish(const NbhdGeo &w, const LevelGeo &g, const NbhdStep &step, const Imgs &A, const JobSet &jobs,
                            const double *rows, const double *q, const int64_t *idx, hipStream_t st);
 // masked resynthesis (ia_mask.hip; include/ia.h ia_synthesize_levels_masked).  The pre-pass sets *err when a
 // pixel's im >= n_ap, or im >= 0 with s outside A.  mask: J x NB bytes, job-major.  count: offsets[t] = where
 // step t's entries start among all T steps' (offsets[T] = the total), entries in (job, row) ascending
-// order; fill: list[offsets[t] ..] = step t's (job, raster index).  gather / finish: ia_launch_nbhd_*'s
-// work for the n queries of one step's list
+// order; fill: list[offsets[t] ..] = step t's (job, raster index), which ia_launch_nbhd_gather / _finish take
+// as a listed NbhdStep
 void ia_launch_mask_check(const int32_t *s, const int32_t *im, int64_t NB, int n_ap, int ah, int aw, unsigned *err,
                           hipStream_t st);
 void ia_launch_mask_count(const uint8_t *mask, int64_t NB, int J, int bh, int bw, int pad, int T, int32_t *offsets,
                           hipStream_t st);
 void ia_launch_mask_fill(const uint8_t *mask, int64_t NB, int J, int bh, int bw, int pad, int T, int32_t *offsets, int2 *list,
                          hipStream_t st);
-void ia_launch_mask_gather(const NbhdGeo &w, const Imgs &B, const JobSet &jobs, const int2 *list, int n, double *q,
-                           hipStream_t st);
-void ia_launch_mask_finish(const NbhdGeo &w, const LevelGeo &g, const Imgs &A, const JobSet &jobs, const int2 *list, int n,
-                           const double *rows, const double *q, const int64_t *idx, hipStream_t st);
 // GPU preprocessing (ia_pyramid.hip)
 void ia_launch_pyramid_reduce(const double *in, double *out, double *tmp, double *sm, double *mm, int h, int w, int ch,
                               const double *w7, hipStream_t st);

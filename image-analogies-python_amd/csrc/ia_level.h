@@ -246,6 +246,15 @@ int build_level_db(ia_ctx *c, LevelPlan &P, const LevelInputs &in, double *ufac)
 int accumulate_stats(ia_ctx *c, const LevelPlan &P, const StampSlots &stamps, const ScanTally &tally, int64_t n_gm,
                      double gather_bytes_timed, ia_stats *stats);
 int accumulate_kcoh_stats(ia_ctx *c, const LevelPlan &P, ia_stats *stats);  // a k-coherence level's
+// What a level of any side path (k-coherence, window, masked) adds: pixels, steps, scan launches, the
+// coherence and kappa counters, and - when the level built a DB - its lv0 / lv1 / lv2 brackets.  tail: the
+// stats words and the two brackets as read, for the caller's own fields.
+struct SideTail {
+  unsigned long long ctr[5] = {0, 0, 0, 0, 0};
+  float ms_db = 0.f, ms_syn = 0.f;
+};
+int accumulate_side_stats(ia_ctx *c, int64_t pixels, int64_t steps, int64_t scans, bool built, ia_stats *stats,
+                          SideTail *tail = nullptr);
 
 // phase 5 (ia_level_run.cpp): the stats words' reduction, the D2H copies of host-memory jobs, the
 // level's one sync, and the error word of the handoffs (chain) and exchanges
@@ -257,13 +266,29 @@ int check_kcoh(ia_ctx *c, const ia_level_args *args, int J, const int32_t *sim, 
 int run_kcoh_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const int32_t *sim_in, int K,
                    ia_stats *stats);
 
-// levels of other window sizes (ia_level_nbhd.cpp): what the sizes, the context and
-// the batch must be for one, and the level after plan_shards and stage_level (P.g.D = w.D)
-// (who: the entry point the refusals name)
+// the side paths' refusal rule (ia_level_nbhd.cpp): sharded, pipelined (a pending ia_pipeline_depend is
+// consumed here) and debug-recording calls; who: the entry point the message names, what: its subject
+int refuse_side_path(ia_ctx *c, const ia_level_args *args, int J, const std::string &who, const std::string &what);
+
+// The two window calls (ia_level_nbhd.cpp; ia_level_mask.cpp, §13).  What the sizes, the
+// context and the batch must be (who: the entry point the refusals name); the prologue after the checks
+// (plan_shards with P.g.D = w.D, stage_level); the window call's level after it.
 int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg, const std::string &who = "ia_synthesize_levels_nbhd");
+int plan_nbhd_level(ia_ctx *c, const ia_level_args *args, int J, const NbhdGeo &w, LevelPlan &P, LevelInputs &in);
 int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const NbhdGeo &w, ia_stats *stats);
-// that call's DB between lv0 and lv1 (fp64 rows, finite check, fp32 tiles; *sc: their prescale), which the
-// masked call (ia_level_mask.cpp) builds too
-int build_nbhd_db(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, const NbhdGeo &w, const std::string &who, double *sc);
+// What a window level's steps share, in the order a level fills it: ensure_nbhd_steps sizes the step
+// buffers (q64, qn2, qf, rec, recT, win, allwin) for a largest step of Mt_max queries and sets the scan's
+// decomposition; build_nbhd_db builds the DB between lv0 and lv1 (fp64 rows, finite check, fp32 tiles)
+// and sets their prescale and the merges' arguments; run_nbhd_step runs one step (ia_launch.h NbhdStep:
+// a wavefront step or a slice of a masked level's list) and returns its scan launches.
+struct NbhdScan {
+  int tpw = 0, nwg = 0;
+  double sc = 1.;
+  MergeArgs ma;
+};
+int ensure_nbhd_steps(ia_ctx *c, const LevelGeo &g, const NbhdGeo &w, int64_t Mt_max, NbhdScan *scan);
+int build_nbhd_db(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, const NbhdGeo &w, const std::string &who, NbhdScan *scan);
+int64_t run_nbhd_step(ia_ctx *c, const LevelGeo &g, const LevelInputs &in, const NbhdGeo &w, const NbhdScan &scan,
+                      const NbhdStep &step);
 
 }  // namespace ia_host

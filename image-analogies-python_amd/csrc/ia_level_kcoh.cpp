@@ -1,6 +1,7 @@
 // ia_level_kcoh.cpp — the k-coherence level (ia_synthesize_levels_kcoh with sim_k > 0, DESIGN.md
 // §10): its checks and its step loop.  It shares the plan's first half, the staging and
-// finish_level with the exact path (ia_level_run.cpp), and none of its steps.
+// finish_level with the exact path (ia_level_run.cpp), and none of its steps; the context refusals are
+// the side paths' one rule (ia_level_nbhd.cpp refuse_side_path).
 #include "ia_level.h"
 
 namespace ia_host {
@@ -12,15 +13,7 @@ int check_kcoh(ia_ctx *c, const ia_level_args *args, int J, const int32_t *sim, 
     return fail(IA_EINVAL, "ia_synthesize_levels_kcoh: sim_k must be 0 (the exact path) or 1..min(IA_KCOH_MAX, N_A - 1)");
   if (!sim_k) return IA_OK;
   if (!sim) return fail(IA_EINVAL, "ia_synthesize_levels_kcoh: sim_k > 0 needs sim");
-  const bool dep = c->dep != nullptr;
-  c->dep = nullptr;  // one level call per ia_pipeline_depend, refused or not
-  c->dep_gen = 0;
-  if (c->world > 1 || c->shard_emulate > 1)
-    return fail(IA_EINVAL, "ia_synthesize_level: k-coherence levels (sim_k > 0) do not run on a sharded or shard-emulating context");
-  if (c->p_record || dep) return fail(IA_EINVAL, "ia_synthesize_level: k-coherence levels (sim_k > 0) are not pipelined");
-  for (int j = 0; j < J; j++)
-    if (args[j].dbg_src) return fail(IA_EINVAL, "ia_synthesize_level: k-coherence levels (sim_k > 0) produce no debug records");
-  return IA_OK;
+  return refuse_side_path(c, args, J, "ia_synthesize_level", "k-coherence levels (sim_k > 0)");
 }
 
 // The level after its staging: the similarity sets checked on the device (one pre-pass, one

@@ -1,9 +1,9 @@
 // ia_level_mask.cpp — masked resynthesis of a level (ia_synthesize_levels_masked): the
-// call, its checks, the step lists and its step loop, and the host statement of the compaction rule
-// (ia_masked_step_list).  It shares the window call's checks and DB (ia_level_nbhd.cpp), the plan's
-// first half, the staging and finish_level; a step is the window call's five launches with the
-// gather and the finish driven by the step's list (ia_mask.hip) instead of the wavefront's geometry,
-// and only the steps that hold a masked pixel run.
+// call, its own checks, the mask pre-pass and step lists (ia_mask.hip), the kept-state copies, the loop
+// over the steps that hold a masked pixel, and the host statement of the compaction rule
+// (ia_masked_step_list).  Everything else is the window call's (ia_level_nbhd.cpp): its checks, prologue,
+// DB, step buffers and its step, run_nbhd_step, given a slice of the list instead of the wavefront's
+// geometry; the stats are the side paths' tail (ia_level_stats.cpp).
 #include <cmath>
 #include <cstring>
 
@@ -26,7 +26,7 @@ struct MaskIn {
 static int run_mask_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const NbhdGeo &w,
                           const MaskIn &mk, ia_stats *stats) {
   const LevelGeo &g = P.g;
-  const int D = w.D, KH = g.KH, J = P.J;
+  const int J = P.J;
   const int64_t NB = P.NB;
   const bool host = args[0].mem == IA_MEM_HOST;
   const hipMemcpyKind in_kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -74,21 +74,11 @@ static int run_mask_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, Le
   int64_t scans = 0;
   float ms_list = 0.f, ms_fill = 0.f;
   hipEventElapsedTime(&ms_list, c->kb[0], c->kb[1]);
-  double *rows = nullptr, *mu = nullptr;
-  double sc = 1.;
-  if (total > 0) {  // the step buffers, and the window call's DB (with its finite check)
-    int tpw, nwg;
-    dense_geometry(g.n_tiles, &tpw, &nwg);
-    const int64_t Mpad_max = tile_pad(Mt_max);
-    if ((rc = c->mk_list.ensure((size_t)total * sizeof(int2))) || (rc = c->q64.ensure((size_t)Mt_max * D * 8)) ||
-        (rc = c->qn2.ensure((size_t)Mpad_max * 8)) || (rc = c->qf.ensure((size_t)Mpad_max * 2 * KH * 4)) ||
-        (rc = c->rec.ensure((size_t)Mt_max * nwg * 16)) || (rc = c->recT.ensure((size_t)Mt_max * nwg * 4)) ||
-        (rc = c->win.ensure((size_t)Mt_max * 8)) || (rc = c->allwin.ensure((size_t)Mt_max * 8)) ||
-        (rc = build_nbhd_db(c, P, in, w, WHO, &sc)))
-      return rc;
-    rows = c->db64.as<double>();
-    mu = c->mu.as<double>();
-  }
+  NbhdScan scan;
+  if (total > 0 &&  // the step buffers, and the window call's DB (with its finite check)
+      ((rc = c->mk_list.ensure((size_t)total * sizeof(int2))) || (rc = ensure_nbhd_steps(c, g, w, Mt_max, &scan)) ||
+       (rc = build_nbhd_db(c, P, in, w, WHO, &scan))))
+    return rc;
   // nothing refuses the call from here on: device-memory jobs take their kept state
   for (int j = 0; j < J && !host; j++) {
     if (mk.s[j] != in.jp[j].s) {
@@ -99,30 +89,14 @@ static int run_mask_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, Le
     }
   }
   if (total > 0) {
-    int tpw, nwg;
-    dense_geometry(g.n_tiles, &tpw, &nwg);
-    double *q64 = c->q64.as<double>();
-    int64_t *idx = c->win.as<int64_t>();
     const int2 *list = c->mk_list.as<int2>();
     HIP_TRY(hipEventRecord(c->kb[2], c->st));
     ia_launch_mask_fill(mask, NB, J, g.bh, g.bw, w.p_l, T, off, c->mk_list.as<int2>(), c->st);
     HIP_TRY(hipEventRecord(c->kb[3], c->st));
-    const MergeArgs ma = dense_merge_args(c->rec.as<float4>(), c->recT.as<float>(), c->qn2.as<double>(), c->Rbits.as<unsigned>(),
-                                          nwg, tpw, g.n_tiles, g.NA, KH);
     for (int t = 0; t < T; t++) {
       const int Mt = off_h[t + 1] - off_h[t];
       if (Mt <= 0) continue;  // only the steps that hold a masked pixel run
-      const int Mpad = (int)tile_pad(Mt);
-      const int2 *lt = list + off_h[t];
-      ia_launch_mask_gather(w, in.Bim, in.jobs(), lt, Mt, q64, c->st);
-      ia_launch_dense_query(KH, q64, Mt, D, Mpad, mu, sc, c->qn2.as<double>(), c->qf.as<float>(), c->st);
-      index_scan_tiles(KH, 0, Mpad / IA_TILE, [&](int qt0, int qt) {
-        ia_launch_k3(KH, qt, c->db.as<float4>(), c->qf.as<float4>(), g.n_tiles, tpw, qt0, Mt, nwg, 0, g.n_tiles,
-                     c->rec.as<float4>(), c->recT.as<float>(), c->st);
-        scans++;
-      });
-      ia_launch_merge_dense(ma, rows, D, q64, Mt, sc * sc, idx, c->allwin.as<double>(), c->st);
-      ia_launch_mask_finish(w, g, in.Aim, in.jobs(), lt, Mt, rows, q64, idx, c->st);
+      scans += run_nbhd_step(c, g, in, w, scan, NbhdStep{StepDesc{}, list + off_h[t], Mt});
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->lv2, c->st));
@@ -131,22 +105,7 @@ static int run_mask_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, Le
   if (total > 0) hipEventElapsedTime(&ms_fill, c->kb[2], c->kb[3]);
   c->mk_levels += J;
   c->mk_list_ms += ms_list + ms_fill;
-  if (!stats) return IA_OK;
-  unsigned long long ctr[5];
-  HIP_TRY(hipMemcpy(ctr, c->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));
-  stats->pixels += total;
-  stats->steps += steps;
-  stats->coherence_wins += (int64_t)ctr[2];
-  stats->kappa_ambiguous += (int64_t)ctr[4];
-  stats->dist_launches += scans;
-  if (total > 0) {
-    float ms_db = 0.f, ms_syn = 0.f;
-    hipEventElapsedTime(&ms_db, c->lv0, c->lv1);
-    hipEventElapsedTime(&ms_syn, c->lv1, c->lv2);
-    stats->db_ms += ms_db;
-    stats->synth_ms += ms_syn;
-  }
-  return IA_OK;
+  return stats ? accumulate_side_stats(c, total, steps, scans, total > 0, stats) : IA_OK;  // (no nbhd_levels: the window call's)
 }
 
 }  // namespace ia_host
@@ -198,11 +157,7 @@ int ia_synthesize_levels_masked(ia_ctx *c, const ia_level_args *args, int n_jobs
   const NbhdGeo w = ia_nbhd_geo(args[0].ch, n_sm, n_lg);
   LevelPlan P;
   LevelInputs in;
-  if ((rc = plan_shards(c, args, n_jobs, P))) return rc;
-  P.g.D = w.D;  // this call's weight length and row width (plan_shards set the 3 / 5 ones)
-  P.g.KH = kh_for(w.D + 1);
-  P.DP = 2 * P.g.KH;
-  if ((rc = stage_level(c, args, P, in))) return rc;
+  if ((rc = plan_nbhd_level(c, args, n_jobs, w, P, in))) return rc;
   return run_mask_level(c, args, P, in, w, MaskIn{mask, s_in, im_in}, stats);
 }
 

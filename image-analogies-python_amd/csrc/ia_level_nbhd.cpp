@@ -1,8 +1,10 @@
 // ia_level_nbhd.cpp — exact levels for window sizes other than 3x3 / 5x5 (ia_synthesize_levels_nbhd,
-// DESIGN.md §11): the call, its checks, its step loop and the wavefront's shape for any skew.  It
-// shares the plan's first half, the staging and finish_level with the default path
-// (ia_level_run.cpp) and none of its steps: a step here is the window kernels of ia_nbhd.hip around
-// the index's query prep, fp32 scan and certified merge (ia_dense.hip, ia_k3.hip).
+// DESIGN.md §11): the call, its checks, its step loop and the wavefront's shape for any skew, and what
+// the masked call (ia_level_mask.cpp) runs too: the prologue, the DB, the step buffers and the step
+// itself (run_nbhd_step: the window kernels of ia_nbhd.hip around the index's query prep, fp32 scan
+// and certified merge, ia_dense.hip, ia_k3.hip).  Here is also the side paths' one refusal rule.
+// These calls share the plan's first half, the staging and finish_level with the default path
+// (ia_level_run.cpp) and none of its steps.
 #include <cmath>
 #include <cstring>
 
@@ -10,10 +12,25 @@
 
 namespace ia_host {
 
-int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg, const std::string &who) {
+// The side paths' refusal rule (this file's two window calls and the k-coherence level,
+// ia_level_kcoh.cpp): their levels run alone on one device, outside the level pipeline, without debug
+// records.  It consumes the pending ia_pipeline_depend, whether it then refuses the call or not.
+// who: the entry point the message names; what: its levels, the sentence's subject.
+int refuse_side_path(ia_ctx *c, const ia_level_args *args, int J, const std::string &who, const std::string &what) {
   const bool dep = c->dep != nullptr;
   c->dep = nullptr;  // one level call per ia_pipeline_depend, refused or not
   c->dep_gen = 0;
+  const std::string subject = who + ": " + what;
+  if (c->world > 1 || c->shard_emulate > 1) return fail(IA_EINVAL, subject + " do not run on a sharded or shard-emulating context");
+  if (c->p_record || dep) return fail(IA_EINVAL, subject + " are not pipelined");
+  for (int j = 0; j < J; j++)
+    if (args[j].dbg_src) return fail(IA_EINVAL, subject + " produce no debug records");
+  return IA_OK;
+}
+
+int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg, const std::string &who) {
+  // first, so that a call refused for its sizes consumes the dependency too; the sizes' message wins
+  const int rc = refuse_side_path(c, args, J, who, "levels of this call");
   const int ch = args[0].ch;
   const NbhdGeo w = ia_nbhd_geo(ch, n_sm, n_lg);
   const bool sizes = (n_sm == 1 || n_sm == 3 || n_sm == 5) && (n_lg == 3 || n_lg == 5 || n_lg == 7 || n_lg == 9);
@@ -23,38 +40,25 @@ int check_nbhd(ia_ctx *c, const ia_level_args *args, int J, int n_sm, int n_lg, 
                                (sizes ? " gives D = " + std::to_string(w.D) + " features" : std::string()) +
                                ": n_sm must be 1, 3 or 5, n_lg 3, 5, 7 or 9, and D = ch (2 n_sm^2 + n_lg^2 + n_lg^2 / 2) <= " +
                                std::to_string(IA_MAX_D - 1));
-  if (c->world > 1 || c->shard_emulate > 1)
-    return fail(IA_EINVAL, who + ": does not run on a sharded or shard-emulating context");
-  if (c->p_record || dep) return fail(IA_EINVAL, who + ": levels of this call are not pipelined");
-  for (int j = 0; j < J; j++)
-    if (args[j].dbg_src) return fail(IA_EINVAL, who + ": produces no debug records");
-  return IA_OK;
+  return rc;
 }
 
-// the level's ia_stats: the pixel counters from the stats words (k_nbhd_finish sets the coherence and
-// kappa bits), the scan launches, and the level's two event brackets
-static int accumulate_nbhd_stats(ia_ctx *c, const LevelPlan &P, int64_t scans, ia_stats *stats) {
-  unsigned long long ctr[5];
-  HIP_TRY(hipMemcpy(ctr, c->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));
-  float ms_db = 0.f, ms_syn = 0.f;
-  hipEventElapsedTime(&ms_db, c->lv0, c->lv1);
-  hipEventElapsedTime(&ms_syn, c->lv1, c->lv2);
-  stats->pixels += P.NB * P.J;
-  stats->steps += P.T;
-  stats->nbhd_levels += P.J;
-  stats->coherence_wins += (int64_t)ctr[2];
-  stats->kappa_ambiguous += (int64_t)ctr[4];
-  stats->dist_launches += scans;
-  stats->db_ms += ms_db;
-  stats->synth_ms += ms_syn;
-  return IA_OK;
+// what both window calls do between their checks and their level: the default plan's first half with
+// this call's weight length and row width in place of the 3 / 5 ones, then the staging
+int plan_nbhd_level(ia_ctx *c, const ia_level_args *args, int J, const NbhdGeo &w, LevelPlan &P, LevelInputs &in) {
+  int rc;
+  if ((rc = plan_shards(c, args, J, P))) return rc;
+  P.g.D = w.D;
+  P.g.KH = kh_for(w.D + 1);
+  P.DP = 2 * P.g.KH;
+  return stage_level(c, args, P, in);
 }
 
 // The window calls' DB (this call's and the masked one's, ia_level_mask.cpp), bracketed by lv0 / lv1:
 // the fp64 rows with their column statistics (one read-back: it also finds a non-finite A side before
 // any step runs; who: the entry point the refusal names), then the index's centred, prescaled fp32
-// tiles.  *sc: their prescale.
-int build_nbhd_db(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, const NbhdGeo &w, const std::string &who, double *sc) {
+// tiles.  Completes scan (after ensure_nbhd_steps): the tiles' prescale and the merges' arguments.
+int build_nbhd_db(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, const NbhdGeo &w, const std::string &who, NbhdScan *scan) {
   const LevelGeo &g = P.g;
   const int D = w.D, KH = g.KH;
   int rc;
@@ -77,59 +81,76 @@ int build_nbhd_db(ia_ctx *c, const LevelPlan &P, const LevelInputs &in, const Nb
   bool finite = std::isfinite(amaxf);
   for (int f = 0; f < D; f++) finite = finite && std::isfinite(mu_h[f]);
   if (!finite) return fail(IA_EINVAL, who + ": the A side must be finite (and its column sums too)");
-  *sc = dense_prescale(amaxf);
-  ia_launch_dense_db(KH, rows, g.NA, D, g.n_tiles, mu, *sc, c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
+  scan->sc = dense_prescale(amaxf);
+  ia_launch_dense_db(KH, rows, g.NA, D, g.n_tiles, mu, scan->sc, c->db.as<float4>(), c->Rbits.as<unsigned>(), c->st);
   HIP_TRY(hipEventRecord(c->lv1, c->st));
+  scan->ma = dense_merge_args(c->rec.as<float4>(), c->recT.as<float>(), c->qn2.as<double>(), c->Rbits.as<unsigned>(), scan->nwg,
+                              scan->tpw, g.n_tiles, g.NA, KH);
   return IA_OK;
 }
 
-// The level after its staging: the DB above, then step t, all jobs: gather the query rows, the
-// index's query prep, its scan in blocks of ia_k3_qtmax(KH) query tiles, its certified merge, then
-// coherence / kappa / writeback: five launches (more scans when the step is wider than one block),
-// nothing fused, nothing pruned.
+// The step buffers of a level whose largest step holds Mt_max queries, and the scan's decomposition.
+int ensure_nbhd_steps(ia_ctx *c, const LevelGeo &g, const NbhdGeo &w, int64_t Mt_max, NbhdScan *scan) {
+  const int64_t Mpad_max = tile_pad(Mt_max);
+  dense_geometry(g.n_tiles, &scan->tpw, &scan->nwg);
+  const int nwg = scan->nwg;
+  int rc;
+  if ((rc = c->q64.ensure((size_t)Mt_max * w.D * 8)) || (rc = c->qn2.ensure((size_t)Mpad_max * 8)) ||
+      (rc = c->qf.ensure((size_t)Mpad_max * 2 * g.KH * 4)) || (rc = c->rec.ensure((size_t)Mt_max * nwg * 16)) ||
+      (rc = c->recT.ensure((size_t)Mt_max * nwg * 4)) || (rc = c->win.ensure((size_t)Mt_max * 8)) ||
+      (rc = c->allwin.ensure((size_t)Mt_max * 8)))
+    return rc;
+  return IA_OK;
+}
+
+// One step of a window level, its queries from the wavefront's geometry or from a masked step's list:
+// gather the query rows, the index's query prep, its scan in blocks of ia_k3_qtmax(KH) query tiles, its
+// certified merge, then coherence / kappa / writeback: five launches (more scans when the step is
+// wider than one block), nothing fused, nothing pruned.  Returns the scan launches.
+int64_t run_nbhd_step(ia_ctx *c, const LevelGeo &g, const LevelInputs &in, const NbhdGeo &w, const NbhdScan &scan,
+                      const NbhdStep &step) {
+  const int D = w.D, KH = g.KH, Mt = step.n, Mpad = (int)tile_pad(Mt);
+  double *rows = c->db64.as<double>(), *mu = c->mu.as<double>(), *q64 = c->q64.as<double>();
+  int64_t *idx = c->win.as<int64_t>();
+  int64_t scans = 0;
+  ia_launch_nbhd_gather(w, step, in.Bim, in.jobs(), q64, c->st);
+  ia_launch_dense_query(KH, q64, Mt, D, Mpad, mu, scan.sc, c->qn2.as<double>(), c->qf.as<float>(), c->st);
+  index_scan_tiles(KH, 0, Mpad / IA_TILE, [&](int qt0, int qt) {
+    ia_launch_k3(KH, qt, c->db.as<float4>(), c->qf.as<float4>(), g.n_tiles, scan.tpw, qt0, Mt, scan.nwg, 0, g.n_tiles,
+                 c->rec.as<float4>(), c->recT.as<float>(), c->st);
+    scans++;
+  });
+  ia_launch_merge_dense(scan.ma, rows, D, q64, Mt, scan.sc * scan.sc, idx, c->allwin.as<double>(), c->st);
+  ia_launch_nbhd_finish(w, g, step, in.Aim, in.jobs(), rows, q64, idx, c->st);
+  return scans;
+}
+
+// The level after its staging: the DB above, then the steps of the schedule t = col + (p_l + 1) row,
+// all jobs in each.
 int run_nbhd_level(ia_ctx *c, const ia_level_args *args, LevelPlan &P, LevelInputs &in, const NbhdGeo &w, ia_stats *stats) {
   const LevelGeo &g = P.g;
-  const int D = w.D, KH = g.KH;
   int rc;
   ia_wavefront_shape_pad(g.bh, g.bw, w.p_l, &P.T, &P.Mmax);
   P.Mtmax = P.Mmax * P.J;
   P.Mpad_max = tile_pad(P.Mtmax);
-  int tpw, nwg;
-  dense_geometry(g.n_tiles, &tpw, &nwg);
-  if ((rc = stage_jobs(c, P, in)) || (rc = c->counters.ensure(5 * 8)) || (rc = c->q64.ensure((size_t)P.Mtmax * D * 8)) ||
-      (rc = c->qn2.ensure((size_t)P.Mpad_max * 8)) || (rc = c->qf.ensure((size_t)P.Mpad_max * 2 * KH * 4)) ||
-      (rc = c->rec.ensure((size_t)P.Mtmax * nwg * 16)) || (rc = c->recT.ensure((size_t)P.Mtmax * nwg * 4)) ||
-      (rc = c->win.ensure((size_t)P.Mtmax * 8)) || (rc = c->allwin.ensure((size_t)P.Mtmax * 8)))
-    return rc;
+  NbhdScan scan;
+  if ((rc = stage_jobs(c, P, in)) || (rc = c->counters.ensure(5 * 8)) || (rc = ensure_nbhd_steps(c, g, w, P.Mtmax, &scan))) return rc;
   HIP_TRY(hipMemsetAsync(c->counters.p, 0, 5 * 8, c->st));
-  double sc;
-  if ((rc = build_nbhd_db(c, P, in, w, "ia_synthesize_levels_nbhd", &sc))) return rc;
-  double *rows = c->db64.as<double>(), *mu = c->mu.as<double>(), *q64 = c->q64.as<double>();
-  int64_t *idx = c->win.as<int64_t>();
-
-  const MergeArgs ma = dense_merge_args(c->rec.as<float4>(), c->recT.as<float>(), c->qn2.as<double>(), c->Rbits.as<unsigned>(),
-                                        nwg, tpw, g.n_tiles, g.NA, KH);
+  if ((rc = build_nbhd_db(c, P, in, w, "ia_synthesize_levels_nbhd", &scan))) return rc;
   int64_t scans = 0;
   for (int64_t t = 0; t < P.T; t++) {
     StepDesc sd{(int)t, 0, 0, 0, P.J};
     ia_wavefront_step_pad(g.bh, g.bw, w.p_l, t, &sd.r0, &sd.M);
     if (sd.M <= 0) continue;  // levels narrower than p_l + 1 columns have empty steps
-    const int Mt = P.J * sd.M;
-    sd.Mpad = (int)tile_pad(Mt);
-    ia_launch_nbhd_gather(w, sd, in.Bim, in.jobs(), q64, c->st);
-    ia_launch_dense_query(KH, q64, Mt, D, sd.Mpad, mu, sc, c->qn2.as<double>(), c->qf.as<float>(), c->st);
-    index_scan_tiles(KH, 0, sd.Mpad / IA_TILE, [&](int qt0, int qt) {
-      ia_launch_k3(KH, qt, c->db.as<float4>(), c->qf.as<float4>(), g.n_tiles, tpw, qt0, Mt, nwg, 0, g.n_tiles,
-                   c->rec.as<float4>(), c->recT.as<float>(), c->st);
-      scans++;
-    });
-    ia_launch_merge_dense(ma, rows, D, q64, Mt, sc * sc, idx, c->allwin.as<double>(), c->st);
-    ia_launch_nbhd_finish(w, g, sd, in.Aim, in.jobs(), rows, q64, idx, c->st);
+    sd.Mpad = (int)tile_pad(P.J * sd.M);
+    scans += run_nbhd_step(c, g, in, w, scan, NbhdStep{sd, nullptr, P.J * sd.M});
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->lv2, c->st));
   if ((rc = finish_level(c, args, P, in, false, stats != nullptr))) return rc;
-  return stats ? accumulate_nbhd_stats(c, P, scans, stats) : IA_OK;
+  if (!stats) return IA_OK;
+  stats->nbhd_levels += P.J;
+  return accumulate_side_stats(c, P.NB * P.J, P.T, scans, true, stats);
 }
 
 }  // namespace ia_host
@@ -166,11 +187,7 @@ int ia_synthesize_levels_nbhd(ia_ctx *c, const ia_level_args *args, int n_jobs, 
   const NbhdGeo w = ia_nbhd_geo(args[0].ch, n_sm, n_lg);
   LevelPlan P;
   LevelInputs in;
-  if ((rc = plan_shards(c, args, n_jobs, P))) return rc;
-  P.g.D = w.D;  // this call's weight length and row width (plan_shards set the 3 / 5 ones)
-  P.g.KH = kh_for(w.D + 1);
-  P.DP = 2 * P.g.KH;
-  if ((rc = stage_level(c, args, P, in))) return rc;
+  if ((rc = plan_nbhd_level(c, args, n_jobs, w, P, in))) return rc;
   return run_nbhd_level(c, args, P, in, w, stats);
 }
 

@@ -1,6 +1,7 @@
 // ia_level_stats.cpp — what a finished level adds to the caller's ia_stats: the counters read
 // back from the device, the event brackets of the sampled steps, and (option "stamps") the
-// per-launch device times of the pruned scan and its merges.
+// per-launch device times of the pruned scan and its merges; and the one tail of the side paths'
+// levels (k-coherence, window, masked).
 #include <cstdio>
 #include <cstdlib>
 
@@ -200,35 +201,45 @@ int accumulate_stats(ia_ctx *c, const LevelPlan &P, const StampSlots &stamps, co
   return IA_OK;
 }
 
-// a k-coherence level (no scan, no tiles): the pixel counters - the stats words carry the
-// candidates where K4 counts reranks and the fallback pixels where it counts rescanned chunks -
-// and the level's two event brackets (K1b is the whole DB build)
+int accumulate_side_stats(ia_ctx *c, int64_t pixels, int64_t steps, int64_t scans, bool built, ia_stats *stats, SideTail *tail) {
+  SideTail t;
+  HIP_TRY(hipMemcpy(t.ctr, c->counters.p, sizeof(t.ctr), hipMemcpyDeviceToHost));
+  stats->pixels += pixels;
+  stats->steps += steps;
+  stats->coherence_wins += (int64_t)t.ctr[2];
+  stats->kappa_ambiguous += (int64_t)t.ctr[4];
+  stats->dist_launches += scans;
+  if (built) {
+    hipEventElapsedTime(&t.ms_db, c->lv0, c->lv1);
+    hipEventElapsedTime(&t.ms_syn, c->lv1, c->lv2);
+    stats->db_ms += t.ms_db;
+    stats->synth_ms += t.ms_syn;
+  }
+  if (tail) *tail = t;
+  return IA_OK;
+}
+
+// a k-coherence level (no scan, no tiles): the side paths' tail, and of its own the stats words that
+// carry the candidates where K4 counts reranks and the fallback pixels where it counts rescanned
+// chunks, and the K1b fields (K1b is the whole DB build)
 int accumulate_kcoh_stats(ia_ctx *c, const LevelPlan &P, ia_stats *stats) {
   const LevelGeo &g = P.g;
-  unsigned long long ctr[5];
-  HIP_TRY(hipMemcpy(ctr, c->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));
-  float ms_db = 0.f, ms_syn = 0.f;
-  hipEventElapsedTime(&ms_db, c->lv0, c->lv1);
-  hipEventElapsedTime(&ms_syn, c->lv1, c->lv2);
+  SideTail t;
+  int rc;
+  if ((rc = accumulate_side_stats(c, P.NB * P.J, P.T, 0, true, stats, &t))) return rc;
   if (g.NA >= stats->build_rows) {
     if (g.NA > stats->build_rows) {
       stats->k1b_ms = stats->k1b_bytes = stats->k1_ms = stats->k1_bytes = 0.;
       stats->build_levels = 0;
       stats->build_rows = g.NA;
     }
-    stats->k1b_ms += ms_db;
+    stats->k1b_ms += t.ms_db;
     stats->k1b_bytes += (double)(P.nA + P.nAc) * (g.n_a + g.n_ap) * 8 + (double)g.NA * ia_db64_stride(g.ch) * 8;
     stats->build_levels += 1;
   }
-  stats->pixels += P.NB * P.J;
-  stats->steps += P.T;
   stats->kcoh_levels += P.J;
-  stats->kcoh_candidates += (int64_t)ctr[0];
-  stats->kcoh_fallbacks += (int64_t)ctr[1];
-  stats->coherence_wins += (int64_t)ctr[2];
-  stats->kappa_ambiguous += (int64_t)ctr[4];
-  stats->db_ms += ms_db;
-  stats->synth_ms += ms_syn;
+  stats->kcoh_candidates += (int64_t)t.ctr[0];
+  stats->kcoh_fallbacks += (int64_t)t.ctr[1];
   return IA_OK;
 }
 

@@ -5,12 +5,11 @@
 //   k_mask_steps     the level's step lists for all jobs, one wave per step of the schedule
 //                    t = col + (p_l + 1) row: a count pass, then (after k_mask_scan) the fill pass
 //   k_mask_scan      the exclusive scan of the counts, in place: offsets[0..T]
-//   k_mask_gather    ia_nbhd.h's gather and finish with the query's pixel taken from the step's
-//   k_mask_finish    list entry (job, raster index) instead of ia_qpix; the finish's coherence pick
-//                    skips cells without a source (NbhdRows<true>)
 //
-// Between gather and finish a step runs the index's kernels unchanged, as ia_nbhd.hip's steps do.
-#include "ia_nbhd.h"
+// A step's list drives the window call's own step (ia_level_nbhd.cpp run_nbhd_step): ia_nbhd.hip's
+// gather and finish kernels in their list form (ia_nbhd.h ListSource).
+#include "ia_dev.h"
+#include "ia_launch.h"
 
 __global__ void __launch_bounds__(IA_WG) k_mask_check(const int32_t *__restrict__ s, const int32_t *__restrict__ im,
                                                       int64_t NB, int n_ap, int ah, int aw, unsigned *__restrict__ err) {
@@ -78,34 +77,6 @@ __global__ void __launch_bounds__(IA_WG) k_mask_scan(int32_t *__restrict__ offse
   }
 }
 
-// query m < n of a step is entry list[m]: its job and raster index
-__device__ __forceinline__ QPix mask_qpix(const int2 *__restrict__ list, int m, int bw) {
-  const int2 e = list[m];
-  QPix p;
-  p.job = e.x;
-  p.qi = e.y;
-  p.r = e.y / bw;
-  p.c = e.y - p.r * bw;
-  return p;
-}
-
-template <class JS>
-__global__ void __launch_bounds__(IA_WG) k_mask_gather(NbhdGeo w, Imgs B, JS jobs, const int2 *__restrict__ list, int n,
-                                                       double *__restrict__ q) {
-  const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
-  if (m >= n) return;
-  nbhd_gather_query(w, B, jobs, mask_qpix(list, m, B.w), m, q);
-}
-
-template <class JS>
-__global__ void __launch_bounds__(IA_WG) k_mask_finish(NbhdGeo w, LevelGeo g, Imgs A, JS jobs, const int2 *__restrict__ list,
-                                                       int n, const double *__restrict__ rows,
-                                                       const double *__restrict__ q64, const int64_t *__restrict__ idx) {
-  const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
-  if (m >= n) return;
-  nbhd_finish_query<true>(w, g, A, jobs, mask_qpix(list, m, g.bw), m, rows, q64, idx);
-}
-
 // ------------------------------------------------------------------------------------------
 // host-side launchers (called from ia_level_mask.cpp)
 // ------------------------------------------------------------------------------------------
@@ -126,20 +97,4 @@ void ia_launch_mask_fill(const uint8_t *mask, int64_t NB, int J, int bh, int bw,
                          hipStream_t st) {
   hipLaunchKernelGGL(k_mask_steps<true>, dim3(cdiv(T, IA_WG / IA_WAVE)), dim3(IA_WG), 0, st, mask, NB, J, bh, bw, pad + 1, T,
                      offsets, list);
-}
-
-void ia_launch_mask_gather(const NbhdGeo &w, const Imgs &B, const JobSet &jobs, const int2 *list, int n, double *q,
-                           hipStream_t st) {
-  const dim3 grid(cdiv(n, IA_WG / IA_WAVE));
-  with_jobs(jobs, B, [&](auto js, const Imgs &Bj) {
-    hipLaunchKernelGGL((k_mask_gather<decltype(js)>), grid, dim3(IA_WG), 0, st, w, Bj, js, list, n, q);
-  });
-}
-
-void ia_launch_mask_finish(const NbhdGeo &w, const LevelGeo &g, const Imgs &A, const JobSet &jobs, const int2 *list, int n,
-                           const double *rows, const double *q, const int64_t *idx, hipStream_t st) {
-  const dim3 grid(cdiv(n, IA_WG / IA_WAVE));
-  with_jobs(jobs, [&](auto js) {
-    hipLaunchKernelGGL((k_mask_finish<decltype(js)>), grid, dim3(IA_WG), 0, st, w, g, A, js, list, n, rows, q, idx);
-  });
 }

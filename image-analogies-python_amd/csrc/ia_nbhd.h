@@ -1,9 +1,33 @@
-// ia_nbhd.h — the window calls' per-query bodies, one wave per query: what the wavefront kernels
-// (ia_nbhd.hip: ia_synthesize_levels_nbhd, the query's pixel from ia_qpix) and the list-driven ones
-// (ia_mask.hip: ia_synthesize_levels_masked, the pixel from the step list) both run.
+// ia_nbhd.h — the window calls' per-query bodies, one wave per query, and the two places a step's
+// queries come from: the wavefront's geometry (ia_synthesize_levels_nbhd) or the step's list
+// (ia_synthesize_levels_masked).  ia_nbhd.hip compiles its gather and finish kernels once per source.
 #pragma once
 #include "ia_certify.h"
 #include "ia_launch.h"
+
+// A step's queries: count() of them, query m at pixel qpix(w, m, width of the B level).  kept: the level
+// holds kept pixels, some without a source (NbhdRows below).
+struct WaveSource {  // step sd of the schedule t = col + (p_l + 1) row, all jobs (ia_qpix)
+  static constexpr bool kept = false;
+  StepDesc sd;
+  __device__ __forceinline__ int count() const { return sd.J * sd.M; }
+  __device__ __forceinline__ QPix qpix(const NbhdGeo &w, int m, int bw) const { return ia_qpix(sd, bw, m, w.p_l + 1); }
+};
+struct ListSource {  // entry m of the step's list: its job and raster index (ia_mask.hip k_mask_steps)
+  static constexpr bool kept = true;
+  const int2 *__restrict__ list;
+  int n;
+  __device__ __forceinline__ int count() const { return n; }
+  __device__ __forceinline__ QPix qpix(const NbhdGeo &, int m, int bw) const {
+    const int2 e = list[m];
+    QPix p;
+    p.job = e.x;
+    p.qi = e.y;
+    p.r = e.y / bw;
+    p.c = e.y - p.r * bw;
+    return p;
+  }
+};
 
 // the fp64 query row of pixel px (query m of its step) into q[m, 0..D)
 template <class JS>
@@ -15,7 +39,7 @@ __device__ __forceinline__ void nbhd_gather_query(const NbhdGeo &w, Imgs B, cons
 }
 
 // these calls' rows as finish_pixel reads them (ia_certify.h LevelRows): N_A x D contiguous.  KEPT:
-// the level holds kept pixels, some without a source (the masked call)
+// the coherence pick skips cells without a source
 template <bool KEPT = false>
 struct NbhdRows {
   static constexpr bool kept = KEPT;

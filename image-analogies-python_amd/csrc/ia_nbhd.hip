@@ -6,10 +6,13 @@
 //                    A' first n_half cells] per pixel (algorithms.py:11-47,50-70)
 //   k_nbhd_colstats  beside it: the D column means and the largest centred |value|, which centre
 //                    and prescale the fp32 copy (ia_dense.hip k_dense_db_build)
-//   k_nbhd_gather    the fp64 query rows of one wavefront step, one wave per query, all jobs
+//   k_nbhd_gather    the fp64 query rows of one step, one wave per query, all jobs
 //   k_nbhd_finish    K4's finish_pixel (ia_certify.h) over this call's rows: best_coherence_match
 //                    over the (p_l + 1) x (2 p_l + 1) window, the kappa rule, the B' / s / im writeback
-//                    (both bodies in ia_nbhd.h, which the masked call's kernels share: ia_mask.hip)
+//                    Both are compiled once per source of the step's queries (ia_nbhd.h): the wavefront's
+//                    geometry for this call, the step's list for the masked one (ia_level_mask.cpp,
+//                    whose list kernels are ia_mask.hip's); the finish's coherence pick skips cells
+//                    without a source only in the list form.
 //
 // Between gather and finish a step runs the index's kernels unchanged: k_dense_query, k3_dist and
 // k_merge_dense (certified_winner over row_dist2_rt), so the NN is the exact fp64 one.
@@ -60,24 +63,24 @@ __global__ void __launch_bounds__(IA_WG) k_nbhd_colstats(const double *__restric
   }
 }
 
-template <class JS>
-__global__ void __launch_bounds__(IA_WG) k_nbhd_gather(NbhdGeo w, StepDesc sd, Imgs B, JS jobs, double *__restrict__ q) {
+template <class SRC, class JS>
+__global__ void __launch_bounds__(IA_WG) k_nbhd_gather(NbhdGeo w, SRC src, Imgs B, JS jobs, double *__restrict__ q) {
   const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
-  if (m >= sd.J * sd.M) return;
-  nbhd_gather_query(w, B, jobs, ia_qpix(sd, B.w, m, w.p_l + 1), m, q);
+  if (m >= src.count()) return;
+  nbhd_gather_query(w, B, jobs, src.qpix(w, m, B.w), m, q);
 }
 
-template <class JS>
-__global__ void __launch_bounds__(IA_WG) k_nbhd_finish(NbhdGeo w, LevelGeo g, StepDesc sd, Imgs A, JS jobs,
+template <class SRC, class JS>
+__global__ void __launch_bounds__(IA_WG) k_nbhd_finish(NbhdGeo w, LevelGeo g, SRC src, Imgs A, JS jobs,
                                                        const double *__restrict__ rows, const double *__restrict__ q64,
                                                        const int64_t *__restrict__ idx) {
   const int m = __builtin_amdgcn_readfirstlane(blockIdx.x * (IA_WG / IA_WAVE) + (threadIdx.x >> 6));  // wave-uniform
-  if (m >= sd.J * sd.M) return;
-  nbhd_finish_query<false>(w, g, A, jobs, ia_qpix(sd, g.bw, m, w.p_l + 1), m, rows, q64, idx);
+  if (m >= src.count()) return;
+  nbhd_finish_query<SRC::kept>(w, g, A, jobs, src.qpix(w, m, g.bw), m, rows, q64, idx);
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side launchers (called from ia_level_nbhd.cpp)
+// host-side launchers (called from ia_level_nbhd.cpp: the DB, and the one step of both window calls)
 // ------------------------------------------------------------------------------------------
 void ia_launch_nbhd_rows(const NbhdGeo &w, const Imgs &A, const APairs &ap, int64_t NA, double *rows, double *mu,
                          unsigned *amax_bits, hipStream_t st) {
@@ -86,17 +89,28 @@ void ia_launch_nbhd_rows(const NbhdGeo &w, const Imgs &A, const APairs &ap, int6
   hipLaunchKernelGGL(k_nbhd_colstats, dim3(w.D), dim3(IA_WG), 0, st, rows, NA, w.D, mu, amax_bits);
 }
 
-void ia_launch_nbhd_gather(const NbhdGeo &w, const StepDesc &sd, const Imgs &B, const JobSet &jobs, double *q, hipStream_t st) {
-  const dim3 grid(cdiv((int64_t)sd.J * sd.M, IA_WG / IA_WAVE));
-  with_jobs(jobs, B, [&](auto js, const Imgs &Bj) {
-    hipLaunchKernelGGL((k_nbhd_gather<decltype(js)>), grid, dim3(IA_WG), 0, st, w, sd, Bj, js, q);
+// the step's source as the kernels' SRC argument: f(src)
+template <class F>
+static inline void with_source(const NbhdStep &step, F &&f) {
+  if (step.list) f(ListSource{step.list, step.n});
+  else f(WaveSource{step.sd});
+}
+
+void ia_launch_nbhd_gather(const NbhdGeo &w, const NbhdStep &step, const Imgs &B, const JobSet &jobs, double *q, hipStream_t st) {
+  const dim3 grid(cdiv(step.n, IA_WG / IA_WAVE));
+  with_source(step, [&](auto src) {
+    with_jobs(jobs, B, [&](auto js, const Imgs &Bj) {
+      hipLaunchKernelGGL((k_nbhd_gather<decltype(src), decltype(js)>), grid, dim3(IA_WG), 0, st, w, src, Bj, js, q);
+    });
   });
 }
 
-void ia_launch_nbhd_finish(const NbhdGeo &w, const LevelGeo &g, const StepDesc &sd, const Imgs &A, const JobSet &jobs,
+void ia_launch_nbhd_finish(const NbhdGeo &w, const LevelGeo &g, const NbhdStep &step, const Imgs &A, const JobSet &jobs,
                            const double *rows, const double *q, const int64_t *idx, hipStream_t st) {
-  const dim3 grid(cdiv((int64_t)sd.J * sd.M, IA_WG / IA_WAVE));
-  with_jobs(jobs, [&](auto js) {
-    hipLaunchKernelGGL((k_nbhd_finish<decltype(js)>), grid, dim3(IA_WG), 0, st, w, g, sd, A, js, rows, q, idx);
+  const dim3 grid(cdiv(step.n, IA_WG / IA_WAVE));
+  with_source(step, [&](auto src) {
+    with_jobs(jobs, [&](auto js) {
+      hipLaunchKernelGGL((k_nbhd_finish<decltype(src), decltype(js)>), grid, dim3(IA_WG), 0, st, w, g, src, A, js, rows, q, idx);
+    });
   });
 }

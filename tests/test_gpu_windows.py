@@ -245,6 +245,57 @@ def test_refusals_leave_outputs_and_context_intact(ctx):
     _same(out[0], Bp[0], WI.run(z1), 2, 'after the refusals')
 
 
+def test_side_calls_share_one_refusal_rule():
+    """The window, masked and k-coherence calls refuse a shard-emulating context and a pending ia_pipeline_depend
+    by one rule: IA_EINVAL, a message naming the entry point and the reason, nothing written - and the refusal
+    consumes the dependency, so the same call on the same context then runs.  One 8 x 8 level, one job."""
+    import ctypes
+    from ia_amd import _native
+    L = _native.lib()
+    z = WI.rand_case(382, 3, 5, geo=dict(a_hw=(8, 8), b_hw=(8, 8), L=2))
+    assert z['A_pyr'][1].shape == z['B_pyr'][1].shape == (8, 8)
+    sim = ((np.arange(64, dtype=np.int32) + 1) % 64).reshape(64, 1).copy()        # valid sets, sim_k = 1
+    mask, s_in, im_in = np.ones(64, dtype=np.uint8), np.zeros((64, 2), dtype=np.int32), np.full(64, -1, dtype=np.int32)
+    one = lambda x: (ctypes.c_void_p * 1)(x.ctypes.data)
+    calls = [
+        ('ia_synthesize_levels_nbhd', lambda c, arr, st: L.ia_synthesize_levels_nbhd(c.handle, arr, 1, 3, 5, st)),
+        ('ia_synthesize_levels_masked', lambda c, arr, st: L.ia_synthesize_levels_masked(c.handle, arr, 1, 3, 5, one(mask),
+                                                                                         one(s_in), one(im_in), st)),
+        ('ia_synthesize_level: k-coherence', lambda c, arr, st: L.ia_synthesize_levels_kcoh(c.handle, arr, 1, _native._ptr(sim),
+                                                                                            1, st)),
+    ]
+
+    def attempt(c, call):
+        Bp = [np.ascontiguousarray(x.copy()) for x in z['Bp_init']]
+        s, im = np.full((64, 2), -7, dtype=np.int32), np.full(64, -7, dtype=np.int32)
+        a, keep = _level_args(z, 1, Bp, s, im)
+        rc = call(c, (_native.LevelArgs * 1)(a), ctypes.byref(_native.Stats()))
+        untouched = bool((s == -7).all() and (im == -7).all() and np.array_equal(Bp[1], z['Bp_init'][1]))
+        return rc, L.ia_last_error().decode() if rc else '', untouched, im
+
+    def refused(c, who, call, reason):
+        rc, msg, untouched, _ = attempt(c, call)
+        assert rc == -1, (who, rc)                                                # IA_EINVAL
+        assert who in msg and reason in msg, msg
+        assert untouched, who
+
+    c2, c3 = _native.Context(0), _native.Context(0)
+    try:
+        c3.set_option('pipeline_record', 1)
+        for who, call in calls:
+            c2.set_option('shard_emulate', 2)
+            refused(c2, who, call, 'shard')
+            c2.set_option('shard_emulate', 1)
+            c2.pipeline_depend(c3, 1)
+            refused(c2, who, call, 'pipelined')
+            rc, msg, _, im = attempt(c2, call)                                    # the dependency was consumed
+            assert rc == 0, (who, rc, msg)
+            assert (im >= 0).all(), who                                           # every pixel took a source
+    finally:
+        c2.close()
+        c3.close()
+
+
 # ---- 9. end to end ----------------------------------------------------------------------------------------
 def test_set_windows_and_synthesize_pyramid(ctx):
     from ia_amd import config, image_analogies as IAm
