@@ -114,6 +114,25 @@ def _blobs():
     return mid[rs.randint(0, 50, 20000)] + 0.05 * rs.randn(20000, 55)
 
 
+def _dupwide_base():
+    return np.random.RandomState(DUPWIDE_SEED).rand(6, 55)
+
+
+def _dupwide():
+    """2400 rows drawn in random order from 6 distinct rows: three lists of two groups each, every distance of a
+    query shared by the about 400 copies of a row, spread over every wave and lane of k_ann_query"""
+    rs = np.random.RandomState(DUPWIDE_SEED + 1)
+    return _dupwide_base()[rs.randint(0, 6, 2400)]
+
+
+def _dupwide_queries():
+    """the 6 distinct rows, then 26 of the rows moved by 1e-2 noise"""
+    rs = np.random.RandomState(DUPWIDE_SEED + 2)
+    base = _dupwide_base()
+    return np.vstack([base, base[rs.randint(0, 6, DUPWIDE_NQ - 6)] + 1e-2 * rs.randn(DUPWIDE_NQ - 6, 55)])
+
+
+DUPWIDE_SEED, DUPWIDE_NQ = 45, 32   # (the seed: the first from 31 up whose three lists hold two of the rows each)
 CASES = {
     'u3000': (_uniform(7, 3000, 55), 32, 5),
     'd3': (_uniform(8, 5000, 3), 40, 50),
@@ -126,8 +145,29 @@ CASES = {
     'w167': (_uniform(13, 200, 167), 4, 5),
     'u3000_it0': (_uniform(7, 3000, 55), 32, 0),
     'n20000': (_uniform(14, 20000, 55), 64, 3),
+    'L4096': (_uniform(15, 8192, 8), 4096, 2),
+    'L1000': (_uniform(16, 6000, 24), 1000, 3),
+    'L300': (_uniform(17, 3000, 55), 300, 3),
+    'd1': (_uniform(18, 500, 1), 10, 5),
+    'dupwide': (_dupwide, 3, 2),
 }
+OWN_QUERIES = {'dupwide': (_dupwide_queries, DUPWIDE_NQ)}   # name -> (generator, nq): not rows of the case plus noise
 GPU_CASES = ('u3000', 'd3', 'each', 'dups', 'blobs', 'one', 'w112', 'w150', 'w167', 'u3000_it0', 'n20000')
+# The sizes at which k_ann_query's loops take their second trip (size trips): more than 256
+# and more than 512 lists (the bitonic sort's and the fill's stride), the full 4,096-list sort area, a prefix that
+# stops in its second block of 64 lists and in a later one, queries at widths 1, 3, 112, 150 and 167, and ties
+# that the merge of the four waves' lists has to cut through.  Built beside GPU_CASES; queried by QUERY_SIZE_RUNS.
+QUERY_SIZE_CASES = ('L4096', 'L1000', 'L300', 'd1', 'dupwide')
+# (case, k, checks, also compared with ExactIndex.query_knn)
+QUERY_SIZE_RUNS = (
+    ('L4096', 1, 1, False), ('L4096', 5, 64, False), ('L4096', 64, 2000, False), ('L4096', 3, -1, True),
+    ('L1000', 5, 600, False), ('L1000', 64, 1500, False), ('L1000', 5, -1, True),
+    ('L300', 5, 1500, False),
+    ('w112', 5, 64, False), ('w112', 5, -1, True), ('w150', 5, 64, False), ('w150', 5, -1, True),
+    ('w167', 5, 64, False), ('w167', 5, -1, True), ('d3', 5, 64, False), ('d3', 5, -1, True),
+    ('d1', 5, 64, False), ('d1', 5, -1, True),
+    ('dupwide', 64, 1, False), ('dupwide', 64, 1000, False),
+)
 UNITS_LOG2 = (-80, 70)
 
 
@@ -160,12 +200,33 @@ def reference(name):
 def queries(name, nq=64):
     """nq queries of the case: the first half exact rows (distance 0 occurs), the rest rows moved by 1e-2 noise"""
     pts = case(name)[0]
+    if name in OWN_QUERIES:
+        gen, own_nq = OWN_QUERIES[name]
+        assert nq == own_nq, (name, nq)
+        q = np.ascontiguousarray(gen())
+        q.setflags(write=False)
+        return q
     rs = np.random.RandomState(21)
     pick = rs.randint(0, len(pts), nq)
     q = pts[pick].copy()
     q[nq // 2:] += 1e-2 * rs.randn(nq - nq // 2, pts.shape[1])
     q.setflags(write=False)
     return q
+
+
+def taken_rows(name, k, checks, nq=64):
+    """per query of the case (rows, dist, pos, list): the rows it takes in probe order, their distances, each
+    row's position inside its list and the list's place in the probe order"""
+    pts = case(name)[0]
+    C, _, _, sizes, rows = reference(name)
+    off = np.concatenate(([0], np.cumsum(sizes)))
+    out = []
+    for q, order in zip(queries(name, nq), probed_lists(name, k, checks, nq)):
+        r = np.concatenate([rows[off[c]:off[c + 1]] for c in order]).astype(np.int64)
+        pos = np.concatenate([np.arange(sizes[c]) for c in order])
+        which = np.concatenate([np.full(sizes[c], i) for i, c in enumerate(order)])
+        out.append((r, ((pts[r] - q) ** 2).sum(axis=1), pos, which))
+    return out
 
 
 def probed_lists(name, k, checks, nq=64):

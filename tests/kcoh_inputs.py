@@ -189,3 +189,39 @@ def expected(name, K, min_rows=1, exact=False):
     if key not in _RUNS:
         _RUNS[key] = run(make(name), K, min_rows, exact)
     return _RUNS[key]
+
+
+# ---- wide32: steps of more than 64 and more than 128 queries ---------------------------------------------------
+WIDE32_K = 4
+for _v in range(4):
+    CASES['wide32_v%d' % _v] = (lambda v: lambda: rand_case(1) if v == 0 else
+                                AI.with_b_side(rand_case(1), rand_case(40 + v), AI.WIDE_K[v]))(_v)
+
+
+def no_base_pixels(s, im, b_hw, a_hw):
+    """the pixels (r, c) of a level without a base row, from its final s / im: a pixel reads raster-earlier
+    pixels only, and those hold their final sources when it is visited"""
+    (h, w), (A_h, A_w) = b_hw, a_hw
+    out = []
+    for qi in range(h * w):
+        r, c = divmod(qi, w)
+        found = False
+        for rr in range(max(0, r - 2), r + 1):
+            for rc in range(max(0, c - 2), min(w, c + 3)):
+                ri = rr * w + rc
+                if ri < qi and 0 <= s[ri, 0] + r - rr < A_h and 0 <= s[ri, 1] + c - rc < A_w:
+                    found = True
+        if not found:
+            out.append((r, c))
+    return out
+
+
+def step_queries(b_hw, J):
+    """{t: {(job, r, c): m}} of the schedule t = col + 3 row with J jobs: k_kcoh_step's query m = job M + (r - r0),
+    M the step's pixels and r0 its first row"""
+    h, w = b_hw
+    out = {}
+    for t in range(w + 3 * (h - 1)):
+        px = [(r, t - 3 * r) for r in range(h) if 0 <= t - 3 * r < w]
+        out[t] = {(j, r, c): j * len(px) + i for j in range(J) for i, (r, c) in enumerate(px)}
+    return out

@@ -194,3 +194,52 @@ def edited(z, rect=(5, 11, 6, 14), seed=9, grow=1):
     z1['B_pyr'] = [np.where(exact[l] if b.ndim == 2 else exact[l][:, :, None], rs.rand(*b.shape), b)
                    for l, b in enumerate(z['B_pyr'][:z['L']])]
     return z1, mask_pyramid(m, shp, grow)
+
+
+# ---- tall: more than 256 steps, and a step of more than 64 rows ------------------------------------------------
+TALL_WIN = (3, 5)
+TALL_GEO = dict(a_hw=(25, 19), b_hw=(66, 200), L=2)
+TALL_T = 200 + 3 * 65            # 395 steps: k_mask_scan's 256 threads take per = 2 steps each
+TALL_LINE_STEP = 197             # the step of the pixels (r, 197 - 3 r), r = 0 .. 65: all 66 rows
+TALL_MASKS = ('line', 'sparse', 'both')
+_TALL = {}
+
+
+def tall():
+    """The case and its kept state, once per process, read-only: dict(z, Bp, s, im, masks).  The state is no
+    finished run (the call's contract takes any valid one): a seeded random source map inside A, im = 0 except
+    about 5 % of the pixels without a source (im = -1), B' = A' at the source and the initial B' where there is
+    none.  masks: 'line' (one step of 66 queries), 'sparse' (a seeded 2 % of the pixels), 'both' (their union)"""
+    if not _TALL:
+        z = WI.rand_case(450, *TALL_WIN, geo=TALL_GEO)
+        h, w = TALL_GEO['b_hw']
+        a_h, a_w = TALL_GEO['a_hw']
+        rs = np.random.RandomState(451)
+        s = np.stack([rs.randint(0, a_h, h * w), rs.randint(0, a_w, h * w)], axis=1).astype(np.int64)
+        im = np.where(rs.rand(h * w) < 0.05, -1, 0).astype(np.int64)
+        Bp = [x.copy() for x in z['Bp_init']]
+        Bp[1] = np.where(im.reshape(h, w) >= 0, z['Ap_pyr'][0][1][s[:, 0], s[:, 1]].reshape(h, w), z['Bp_init'][1])
+        line = np.zeros((h, w), dtype=bool)
+        line[np.arange(h), TALL_LINE_STEP - 3 * np.arange(h)] = True
+        sparse = rs.rand(h, w) < 0.02
+        for x in (s, im, line, sparse, *Bp):
+            x.setflags(write=False)
+        _TALL.update(z=z, Bp=Bp, s=s, im=im, masks=dict(line=line, sparse=sparse, both=line | sparse))
+    return _TALL
+
+
+_TALL_RUNS = {}
+
+
+def tall_expected(kind):
+    """resynthesize() of tall's state under mask `kind`, once per process; read-only"""
+    if kind not in _TALL_RUNS:
+        t = tall()
+        _TALL_RUNS[kind] = resynthesize(t['z'], [x.copy() for x in t['Bp']], {1: t['masks'][kind]}, {1: t['s']}, {1: t['im']})
+    return _TALL_RUNS[kind]
+
+
+def scan_shares(T, threads=256):
+    """k_mask_scan's split of the T step counts: (per, [(a, b)] per thread), thread i sums offsets[a:b]"""
+    per = -(-T // threads)
+    return per, [(min(T, i * per), min(T, min(T, i * per) + per)) for i in range(threads)]

@@ -71,7 +71,7 @@ def test_assign_is_the_per_row_rule(name):
         assert np.array_equal(A.assign_ref(pts, C), A.assign_per_row(pts, C))
 
 
-@pytest.mark.parametrize('name', A.GPU_CASES)
+@pytest.mark.parametrize('name', A.GPU_CASES + A.QUERY_SIZE_CASES)
 def test_every_row_sits_with_its_nearest_centre(name):
     """a == assign(C) on the returned centres; the lists partition the rows, each ascending"""
     pts, L, _ = A.case(name)
@@ -106,6 +106,85 @@ def test_case_claims():
     assert A.reference('one')[3].tolist() == [1]
     assert [A.case(n)[0].shape[1] for n in ('w112', 'w150', 'w167')] == [112, 150, 167]   # 150, 167: the split sum
     assert A.case('n20000')[0].shape == (20000, 55) and A.reference('n20000')[2] == 3
+
+
+def _probed(name, k, checks, nq=64):
+    _, _, taken, probed = A.query_reference(name, k, checks, nq)
+    print('%s (%d, %d): lists probed %d..%d, rows taken %d..%d' % (name, k, checks, probed.min(), probed.max(), taken.min(),
+                                                                   taken.max()))
+    return probed
+
+
+def test_query_size_case_claims():
+    """what each case of QUERY_SIZE_CASES is there for: the loops of k_ann_query that GPU_CASES' at most 128 lists
+    run once or not at all (P = the lists rounded up to a power of two: the sort area)"""
+    P = lambda L: 1 << (L - 1).bit_length()
+    assert set(A.QUERY_SIZE_CASES) <= set(A.CASES) and not set(A.QUERY_SIZE_CASES) & set(A.GPU_CASES)
+    assert {n for n, _, _, _ in A.QUERY_SIZE_RUNS} == set(A.QUERY_SIZE_CASES) | {'w112', 'w150', 'w167', 'd3'}
+    # L4096: the full sort area; lists of 1 .. 8 rows, so k_ann_update's unroll by 4 sees every remainder
+    pts, L, iters = A.case('L4096')
+    _, _, run, sizes, _ = A.reference('L4096')
+    assert pts.shape == (8192, 8) and L == P(L) == A.ANN_MAX_LISTS == 4096 and iters == 2 and run <= 2
+    assert 1 <= sizes.min() and sizes.max() <= 8 and all((sizes == s).any() for s in (1, 2, 3, 4, 5)) and (sizes >= 6).any()
+    assert {(int(s) - 1) % 4 for s in np.unique(sizes)} == {0, 1, 2, 3}       # the rows after a list's first, mod 4
+    assert (_probed('L4096', 1, 1) >= 1).all()
+    p = _probed('L4096', 5, 64)
+    assert (p > 16).all()
+    p = _probed('L4096', 64, 2000)
+    assert (p > 512).all() and (p < L).all()
+    assert (_probed('L4096', 3, -1) == L).all()
+    # L1000: P = 1,024 with 24 padding slots; 512 pairs: two strided trips of the sort
+    pts, L, iters = A.case('L1000')
+    assert pts.shape == (6000, 24) and (L, P(L), iters) == (1000, 1024, 3) and P(L) // 2 == 2 * 256
+    p = _probed('L1000', 5, 600)
+    assert (p > 64).all() and (p <= 128).all()                                # the prefix stops inside its second block
+    p = _probed('L1000', 64, 1500)
+    assert (p > 128).all() and (p < L).all()                                  # third block or later: cum carried twice
+    assert (_probed('L1000', 5, -1) == L).all()
+    # L300: P = 512: one full trip of 256 pairs, two trips of the fill
+    pts, L, iters = A.case('L300')
+    assert pts.shape == (3000, 55) and (L, P(L)) == (300, 512) and P(L) // 2 == 256 and P(L) == 2 * 256
+    p = _probed('L300', 5, 1500)
+    assert (p > 64).all() and (p < L).all()
+    # the widths
+    assert [A.case(n)[0].shape[1] for n in ('w112', 'w150', 'w167', 'd3', 'd1')] == [112, 150, 167, 3, 1]
+    assert A.case('d1')[0].shape == (500, 1) and A.case('d1')[1] == 10
+    for name in ('w112', 'w150', 'w167', 'd3', 'd1'):
+        assert (name, 5, 64, False) in A.QUERY_SIZE_RUNS and (name, 5, -1, True) in A.QUERY_SIZE_RUNS
+        assert (_probed(name, 5, -1) == A.case(name)[1]).all()
+
+
+@pytest.mark.parametrize('name,k', [('L4096', 3), ('L1000', 5), ('w112', 5), ('w150', 5), ('w167', 5), ('d3', 5), ('d1', 5)])
+def test_query_size_unlimited_checks_is_the_exact_knn(name, k):
+    i_ref, d_ref = K.knn_reference(A.case(name)[0], A.queries(name), k)
+    idx, dist, taken, _ = A.query_reference(name, k, -1)
+    assert np.array_equal(idx, i_ref) and np.array_equal(dist, d_ref) and (taken == len(A.case(name)[0])).all()
+
+
+def test_dupwide_ties_cut_through_the_waves():
+    """2,400 rows, 6 distinct, three lists of two of them each: a query's distance is shared by the about 400 copies
+    of a row, which stand at every second position of their list or so, i.e. on every wave and lane of
+    k_ann_query's stride; k = 64 cuts that group, so the answer is its 64 lowest row indices, which no wave holds
+    alone.  (Copies of one row share one list, so at checks = 1000 the second list adds farther rows only.)"""
+    pts, L, iters = A.case('dupwide')
+    _, a, run, sizes, rows = A.reference('dupwide')
+    assert pts.shape == (2400, 55) and (L, iters) == (3, 2) and len(np.unique(pts, axis=0)) == 6
+    print('dupwide lists', sizes.tolist(), 'iterations', run)
+    assert (sizes >= 700).all() and (sizes <= 900).all()
+    assert all(len(np.unique(pts[a == c], axis=0)) == 2 for c in range(3))
+    q = A.queries('dupwide', A.DUPWIDE_NQ)
+    assert q.shape == (32, 55) and np.array_equal(np.unique(q[:6], axis=0), np.unique(pts, axis=0))
+    for checks, lists in ((1, 1), (1000, 2)):
+        idx, dist, taken, probed = A.query_reference('dupwide', 64, checks, A.DUPWIDE_NQ)
+        assert (probed == lists).all()
+        for j, (r, dd, pos, which) in enumerate(A.taken_rows('dupwide', 64, checks, A.DUPWIDE_NQ)):
+            o = np.lexsort((r, dd))
+            assert dd[o[63]] == dd[o[64]] and (dd == dd[o[0]]).sum() >= 350        # the 64th and 65th candidates tie
+            assert np.array_equal(idx[j], r[o[:64]]) and (np.diff(idx[j]) > 0).all() and (dist[j] == dd[o[0]]).all()
+            assert len(set(((pos[o[:64]] // 64) % 4).tolist())) > 1                 # not one wave's stride
+            assert (which[o[:64]] == 0).all()
+            if j < 6:                                                               # a distinct row itself
+                assert dd[o[0]] == 0 and np.array_equal(r[o[:64]], np.flatnonzero((pts == q[j]).all(axis=1))[:64])
 
 
 def test_dups_queries_cross_empty_lists():

@@ -53,12 +53,13 @@ def _check_build(name, centers, assign, run, sizes, rows):
 
 
 # ---- 1. k-means and the lists ----------------------------------------------------------------------------
-@pytest.mark.parametrize('name', A.GPU_CASES)
+@pytest.mark.parametrize('name', A.GPU_CASES + A.QUERY_SIZE_CASES)
 def test_kmeans_and_lists(ctx, ann_of, name):
     """ia_kmeans and ia_ann_build + ia_ann_lists: the centres, assign, iters_run, sizes and rows of the numpy rule
     (u3000: every iteration; d3: the early exit and sums of fewer than 8 terms; each: one row per list; dups:
     equal centres, empty lists; w150 / w167: the split pairwise sum; u3000_it0: no iteration; n20000: 105
-    workgroups of 192 rows)"""
+    workgroups of 192 rows; QUERY_SIZE_CASES - L4096: lists of 1 .. 7 rows, every remainder of k_ann_update's
+    unroll by 4, and 256 blocks of centres in k_ann_assign; d1: one column; dupwide: 400 equal rows a centre)"""
     pts, L, iters = A.case(name)
     centers, assign, run = _native().kmeans(ctx, pts, L, iters)
     _check_build(name, centers, assign, run, None, None)
@@ -126,6 +127,39 @@ def test_empty_and_tiny_lists(ann_of):
         _check_query(ann_of('dups'), 'dups', A.DUPS_K, checks)
     _check_query(ann_of('each'), 'each', 5, 1)
     assert ann_of('each').stats()[:2] == (5 * 64, 5 * 64)
+
+
+_exact = {}
+
+
+@pytest.fixture(scope='module')
+def exact_of(ctx):
+    """case name -> its ExactIndex, built once per module"""
+    def get(name):
+        if name not in _exact:
+            _exact[name] = _native().ExactIndex(ctx, A.case(name)[0])
+        return _exact[name]
+    yield get
+    for a in _exact.values():
+        a.close()
+    _exact.clear()
+
+
+@pytest.mark.parametrize('name,k,checks,exact', A.QUERY_SIZE_RUNS, ids=['%s-k%d-c%d' % r[:3] for r in A.QUERY_SIZE_RUNS])
+def test_query_sizes(ann_of, exact_of, name, k, checks, exact):
+    """the sizes at which k_ann_query's loops take another trip (tests/test_ann_cpu.py pins each): L4096 - the full
+    4,096-entry sort area, 8 strided trips of the sort, a prefix over up to 1,003 lists; L1000 - 24 padding slots,
+    two trips, a prefix that stops in its second block of 64 lists (checks 600) and in its third or fourth (1500);
+    L300 - exactly one full trip of 256 pairs and two of the fill; queries at widths 112, 150, 167, 3 and 1;
+    dupwide - k = 64 cuts a group of about 400 rows at one distance that stand on every wave and lane, so the
+    merge of the four waves' lists decides by the row index alone.  checks = -1 is the exact index's answer too."""
+    nq = A.DUPWIDE_NQ if name == 'dupwide' else 64
+    idx, dist = _check_query(ann_of(name), name, k, checks, nq)
+    if exact:
+        i_ex, d_ex = exact_of(name).query_knn(A.queries(name), k)
+        assert np.array_equal(idx, i_ex) and np.array_equal(dist, d_ex)
+    if name == 'dupwide':
+        assert (dist[:6] == 0).all() and (dist == dist[:, :1]).all() and (np.diff(idx, axis=1) > 0).all()
 
 
 def test_batches(ann_of):

@@ -158,6 +158,29 @@ def test_batch_of_three_jobs_equals_separate_calls(ctx):
     assert st.kcoh_candidates == sum(e['candidates'][1] for e in E)
 
 
+def test_wide_32_jobs_fallbacks_beyond_the_first_64_queries(ctx):
+    """32 jobs on main's A side (job j = variant j mod 4, K = 4) in one call: steps of up to 160 queries, which
+    the scan waves test 64 at a time.  tests/test_kcoh_cpu.py pins pixels without a base row at queries 64 ..
+    115 of step 9 and at 130 and 150 of step 21: the second and third trip find them, scan the DB for them and
+    finish them.  Every job equals its variant's restatement.
+    The call runs after one that leaves other, valid sources in all 32 jobs' s / im buffers (the jobs rotated by one
+    variant, on the exact path, result not looked at): a pixel that no wave finished then keeps another job's
+    source - wrong, and not whatever a fresh allocation holds."""
+    names = ['wide32_v%d' % v for v in range(4)]
+    V, E = [KI.make(n) for n in names], [KI.expected(n, KI.WIDE32_K) for n in names]
+    assert all(np.array_equal(e['sim'][1], E[0]['sim'][1]) for e in E)   # one A side
+    for i in range(4):
+        for j in range(i):
+            assert not np.array_equal(E[i]['s'][1], E[j]['s'][1])
+    _run(ctx, [V[(j + 1) % 4] for j in range(32)], {})
+    out, Bp, st = _run(ctx, [V[j % 4] for j in range(32)], E[0]['sim'])
+    for j in range(32):
+        _same(out[j], Bp[j], E[j % 4], [1])
+    assert st.kcoh_levels == 32 and st.pixels == 32 * 143 and st.dist_launches == 0
+    assert st.kcoh_fallbacks == 8 * sum(e['fallbacks'][1] for e in E) == 136
+    assert st.kcoh_candidates == 8 * sum(e['candidates'][1] for e in E)
+
+
 # ---- 5. device pointers -----------------------------------------------------------------------------------
 def _device_level(z, level, Bp, sim):
     """the tensors of one level on cuda:0, sim included"""

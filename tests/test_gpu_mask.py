@@ -250,6 +250,83 @@ def test_borders_narrower_than_the_pad(ctx):
     _same(out[0], Bp, want, 2, 'random')
 
 
+def _tall_redo(ctx, kinds, st=None):
+    """mask_inputs.tall's state under the masks `kinds` (None: all-zero), one job each in one call.  Returns
+    ([(s, im)] per job, [B'] per job)"""
+    t = MI.tall()
+    z = t['z']
+    masks = [np.zeros((66, 200), dtype=bool) if k is None else t['masks'][k] for k in kinds]
+    Bp = [_copy(t['Bp']) for _ in kinds]
+    out = _redo(ctx, [z] * len(kinds), MI.TALL_WIN, Bp, [{1: m} for m in masks], [{1: t['s']}] * len(kinds),
+                [{1: t['im']}] * len(kinds), st)
+    return [o[1] for o in out], [b[1] for b in Bp], masks
+
+
+def _tall_same(got, Bp, kind):
+    t = MI.tall()
+    if kind is None:                                             # an all-zero mask: the state as it was
+        want_s, want_im, want_Bp = t['s'], t['im'], t['Bp'][1]
+    else:
+        e = MI.tall_expected(kind)
+        want_s, want_im, want_Bp = e['s'][1], e['im'][1], e['Bp'][1]
+        kept = ~t['masks'][kind].ravel()                         # kept pixels are untouched
+        assert np.array_equal(got[0][kept], t['s'][kept]) and np.array_equal(got[1][kept], t['im'][kept]), kind
+        assert np.array_equal(Bp.ravel()[kept], t['Bp'][1].ravel()[kept]), kind
+    assert np.array_equal(got[0], want_s), (kind, 's')
+    assert np.array_equal(got[1], want_im), (kind, 'im')
+    assert np.array_equal(Bp, want_Bp), (kind, 'Bp')
+
+
+@pytest.mark.parametrize('kind', MI.TALL_MASKS)
+def test_tall_level_more_than_256_steps_and_a_step_of_66_rows(ctx, kind):
+    """B 66 x 200 at (3, 5): 395 steps, so every thread of k_mask_scan sums a share of two counts ('sparse': masked
+    pixels on both sides of step 256); 'line' is step 197 with all 66 rows masked: three query tiles, rows 64 and
+    65 placed by k_mask_steps' second trip behind the 64 of the first ('both': among sparse steps)"""
+    from ia_amd import _native
+    st = _native.Stats()
+    got, Bp, masks = _tall_redo(ctx, [kind], st)
+    _tall_same(got[0], Bp[0], kind)
+    e = MI.tall_expected(kind)
+    assert st.pixels == int(masks[0].sum()) and st.steps == MI.nonempty_steps(masks, 2)
+    assert st.coherence_wins == MI.wins(e['log'][1]) and st.kappa_ambiguous == 0
+    if kind == 'line':
+        assert st.steps == 1 and st.pixels == 66
+
+
+def test_tall_batch_of_three_jobs_equals_separate_calls(ctx):
+    """jobs 'line', 'sparse' and an all-zero mask in one call: a step's entries stand job after job, so the count
+    carried over step 197's 64-row trips goes on into the next job's entries"""
+    from ia_amd import _native
+    kinds = ['line', 'sparse', None]
+    st = _native.Stats()
+    got, Bp, masks = _tall_redo(ctx, kinds, st)
+    for j, kind in enumerate(kinds):
+        _tall_same(got[j], Bp[j], kind)
+        one, Bp1, _ = _tall_redo(ctx, [kind])
+        assert np.array_equal(one[0][0], got[j][0]) and np.array_equal(one[0][1], got[j][1]) and np.array_equal(Bp1[0], Bp[j])
+    assert st.pixels == 66 + int(masks[1].sum()) and st.steps == MI.nonempty_steps(masks, 2)
+    assert MI.nonempty_steps(masks, 2) == MI.nonempty_steps([masks[0] | masks[1]], 2)
+
+
+def test_tall_both_on_device_memory(ctx):
+    tl = MI.tall()
+    z, e, mask = tl['z'], MI.tall_expected('both'), tl['masks']['both']
+    t = lambda x, dt=np.float64: torch.from_numpy(np.array(x, dtype=dt, order='C')).to('cuda:0')   # (copies: the state is read-only)
+    n = mask.size
+    T = dict(A=t(z['A_pyr'][1]), Ac=t(z['A_pyr'][0]), Ap=t(np.stack([p[1] for p in z['Ap_pyr']])),
+             Apc=t(np.stack([p[0] for p in z['Ap_pyr']])), B=t(z['B_pyr'][1]), Bc=t(z['B_pyr'][0]), Bpc=t(tl['Bp'][0]),
+             Bp=t(tl['Bp'][1]), weights=t(z['weights']), s_out=torch.full((n, 2), -7, dtype=torch.int32, device='cuda:0'),
+             im_out=torch.full((n,), -7, dtype=torch.int32, device='cuda:0'), mask=t(mask, np.uint8),
+             s_in=t(tl['s'], np.int32), im_in=t(tl['im'], np.int32))
+    torch.cuda.synchronize()
+    ctx.resynthesize_levels_device(1, 1, (25, 19), (66, 200), [{k: v.data_ptr() for k, v in T.items()}],
+                                   [1 + (2 ** (1 - z['L'])) * z['k']], windows=MI.TALL_WIN)
+    torch.cuda.synchronize()
+    assert np.array_equal(T['s_out'].cpu().numpy(), e['s'][1]) and np.array_equal(T['im_out'].cpu().numpy(), e['im'][1])
+    assert np.array_equal(T['Bp'].cpu().numpy(), e['Bp'][1])
+    assert np.array_equal(T['s_in'].cpu().numpy(), tl['s']) and np.array_equal(T['im_in'].cpu().numpy(), tl['im'])
+
+
 # ---- 6. a batch -------------------------------------------------------------------------------------------------
 def test_a_batch_of_three_masks_equals_separate_calls_and_the_restatement(ctx):
     """job 0: an all-zero mask on the finished state; job 1: a full mask from the initial B' without sources;

@@ -131,6 +131,33 @@ def test_certification_edges_equal_the_restatement(ctx, name):
     _check_case(ctx, name)
 
 
+@pytest.mark.parametrize('mem', ['host', 'device'])
+def test_big_db_rows_past_the_first_grid_trip(ctx, mem):
+    """edge_bigA_3_9: 8,280 rows x 139 = 1,150,920 DB elements, 102,344 more than k_nbhd_rows' 4,096 x 256 grid,
+    so its grid-stride loop takes a second trip for the rows from 7,543 on (tests/test_windows_cpu.py pins that
+    5 final sources and 12 NN rows lie there).  It runs after calls that leave other rows in the context's DB
+    buffer - the cases above, and first, here, bigA_neartie at the same sizes, whose result is not looked at -
+    so a tail that was not written holds another A's rows at these very places: wrong, not accidentally right."""
+    from ia_amd import _native
+    name = 'edge_bigA_3_9'
+    z, e = WI.make(name), WI.expected(name)
+    _run(ctx, [WI.sized(WI.AI.make('bigA_neartie'), 3, 9)], (3, 9))
+    T, mmax, tiles = WI.step_shape(12, 16, 4)
+    if mem == 'host':
+        st = _check_case(ctx, name)
+        assert st.nbhd_levels == 1 and st.steps == T == 71 and st.dist_launches == tiles == T    # one query tile a step
+        return
+    st = _native.Stats()
+    Bp = [x.copy() for x in z['Bp_init']]
+    D = _device_level(z, 1, Bp)
+    ctx.synthesize_level_device(1, 1, z['A_pyr'][1].shape[:2], z['B_pyr'][1].shape[:2], {k: v.data_ptr() for k, v in D.items()},
+                                1 + (2 ** (1 - z['L'])) * z['k'], st, windows=(3, 9))
+    torch.cuda.synchronize()
+    assert np.array_equal(D['s_out'].cpu().numpy(), e['s'][1]) and np.array_equal(D['im_out'].cpu().numpy(), e['im'][1])
+    assert np.array_equal(D['Bp'].cpu().numpy(), e['Bp'][1])
+    assert st.nbhd_levels == 1 and st.steps == T and st.dist_launches == tiles
+
+
 # ---- 6. training pairs ------------------------------------------------------------------------------------
 def test_pairs_equal_the_restatement(ctx):
     z = WI.make('pairs2')

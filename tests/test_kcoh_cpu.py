@@ -71,6 +71,39 @@ def test_small_k_leaves_few_fallbacks_and_is_not_the_exact_path():
         assert not np.array_equal(kc['s'][1], ex['s'][1])
 
 
+# the pixels without a base row of wide32's four variants (K = 4), as KI.no_base_pixels finds them in the
+# restatement's final s / im
+WIDE32_NO_BASE = {0: [(0, 0), (0, 3), (0, 8), (0, 9), (3, 0)], 1: [(0, 0), (0, 7)],
+                  2: [(0, 0), (0, 5), (0, 10), (1, 0), (3, 12), (6, 10)], 3: [(0, 0), (0, 10), (8, 10), (8, 12)]}
+
+
+def test_wide32_puts_fallback_pixels_into_the_scan_waves_second_and_third_trip():
+    """32 jobs on main's A side, job j = variant j mod 4: steps of up to 160 queries, which k_kcoh_step's scan
+    waves test 64 at a time; a pixel without a base row at query m >= 64 and at m >= 128 makes their second and
+    third trip do work (part[m H + h] and cnt[m] there)"""
+    b_hw, a_hw = (11, 13), (12, 10)
+    fb = {}
+    for v in range(4):
+        z, e = KI.make('wide32_v%d' % v), KI.expected('wide32_v%d' % v, KI.WIDE32_K)
+        assert z['B_pyr'][1].shape == b_hw and z['A_pyr'][1].shape == a_hw and KI.n_rows(z, 1) == 120
+        assert np.array_equal(z['A_pyr'][1], KI.make('main')['A_pyr'][1]) and e['kcoh_levels'] == [1]
+        fb[v] = KI.no_base_pixels(e['s'][1], e['im'][1], b_hw, a_hw)
+        assert fb[v] == WIDE32_NO_BASE[v] and len(fb[v]) == e['fallbacks'][1]
+    assert -(-120 // 64) == 2                                       # H: the scan waves at 120 rows
+    steps = KI.step_queries(b_hw, 32)
+    assert len(steps) == 43 and max(len(q) for q in steps.values()) == 160
+    at = {t: sorted(m for (j, r, c), m in q.items() if (r, c) in fb[j % 4]) for t, q in steps.items()}
+    # step 9, (0, 9) (1, 6) (2, 3) (3, 0): two fallbacks per variant-0 job, jobs 16 .. 28 in the second trip
+    assert at[9] == sorted(m for j in range(0, 32, 4) for m in (4 * j, 4 * j + 3))
+    assert [m for m in at[9] if 64 <= m < 128] == [64, 67, 80, 83, 96, 99, 112, 115]
+    # step 10, (0, 10) (1, 7) (2, 4) (3, 1): variants 2 and 3 in one ballot
+    assert at[10] == sorted(4 * j for j in range(32) if j % 4 in (2, 3)) and {8, 12} <= set(at[10])
+    # step 21, (3, 12) .. (7, 0): variant 2's (3, 12) at m = 5 j, up to the third trip
+    assert at[21] == [5 * j for j in range(2, 32, 4)] == [10, 30, 50, 70, 90, 110, 130, 150]
+    assert any(64 <= m < 128 for ms in at.values() for m in ms) and any(m >= 128 for ms in at.values() for m in ms)
+    assert sum(len(ms) for ms in at.values()) == 8 * sum(len(v) for v in fb.values()) == 136
+
+
 def test_chained_levels_switch_at_min_rows():
     """the pyramid case: 30 and 120 DB rows; min_rows = 100 leaves level 1 exact"""
     both, fine = KI.expected('pyr', 4), KI.expected('pyr', 4, min_rows=100)

@@ -122,6 +122,53 @@ def test_step_list_offsets_only_and_refusals():
         assert b'ia_masked_step_list' in L.ia_last_error()
 
 
+def test_tall_case_has_two_steps_a_scan_thread_and_a_step_of_66_rows():
+    """mask_inputs.tall (B 66 x 200 at (3, 5)): 395 steps, so each of k_mask_scan's 256 threads sums a share of two
+    counts, and step 197 holds all 66 rows, two of them in k_mask_steps' second 64-row trip"""
+    t = MI.tall()
+    z, masks = t['z'], t['masks']
+    h, w = z['B_pyr'][1].shape
+    assert (h, w) == (66, 200) and z['win'] == (3, 5) and z['L'] == 2
+    T = w + 3 * (h - 1)
+    assert T == MI.TALL_T == 395 and _native.wavefront_shape_pad(h, w, 2) == (395, 66)
+    per, shares = MI.scan_shares(T)
+    assert per == 2 and shares[0] == (0, 2) and shares[128] == (256, 258) and shares[197] == (394, 395)
+    assert all(a == b == T for a, b in shares[198:])                 # the shares from 198 up are empty
+    assert _native.wavefront_step_pad(h, w, 2, MI.TALL_LINE_STEP) == (0, 66)
+    # the kept state: valid sources, about 5 % without one, B' = A' at the source
+    s, im = t['s'], t['im']
+    assert ((s >= 0) & (s < [25, 19])).all() and set(np.unique(im)) == {-1, 0} and 0.04 < (im < 0).mean() < 0.06
+    has = (im >= 0).reshape(h, w)
+    assert np.array_equal(t['Bp'][1][has], z['Ap_pyr'][0][1][s[:, 0], s[:, 1]].reshape(h, w)[has])
+    assert np.array_equal(t['Bp'][1][~has], z['Bp_init'][1][~has]) and np.array_equal(t['Bp'][0], z['Bp_init'][0])
+    # the masks
+    line, sparse, both = masks['line'], masks['sparse'], masks['both']
+    assert line.sum() == 66 and [tuple(x) for x in np.argwhere(line)] == [(r, 197 - 3 * r) for r in range(66)]
+    off = MI.step_list(line, 2)[0]
+    assert np.diff(off).max() == 66 and off[197] == 0 and off[198] == 66
+    assert 0.015 < sparse.mean() < 0.025 and np.array_equal(both, line | sparse) and (line & ~sparse).sum() >= 60
+    off = MI.step_list(sparse, 2)[0]
+    assert (off[256], off[-1] - off[256]) == (202, 72)               # masked pixels in steps on both sides of index 256
+    assert int(np.count_nonzero(np.diff(off)[1::2])) > 0             # a share's second count is non-zero: a real sum
+    assert np.diff(MI.step_list(both, 2)[0]).max() >= 66
+    for name in MI.TALL_MASKS:                                       # the host statement of the compaction
+        o, px = _native.masked_step_list(masks[name], 2)
+        eo, ep = MI.step_list(masks[name], 2)
+        assert np.array_equal(o, eo) and np.array_equal(px, ep), name
+
+
+def test_tall_restatements_redo_the_masked_pixels_only():
+    t = MI.tall()
+    for name, n, wins in (('line', 66, 27), ('sparse', 274, 140), ('both', 340, 170)):
+        r, m = MI.tall_expected(name), t['masks'][name].ravel()
+        assert m.sum() == n == len(r['log'][1]) and MI.wins(r['log'][1]) == wins
+        assert np.array_equal(r['s'][1][~m], t['s'][~m]) and np.array_equal(r['im'][1][~m], t['im'][~m])
+        assert np.array_equal(r['Bp'][1].ravel()[~m], t['Bp'][1].ravel()[~m]) and (r['im'][1][m] == 0).all()
+        assert (r['s'][1][m] != t['s'][m]).any(axis=1).sum() > n // 2     # the redone pixels took other sources
+        for _, rec, kf in r['log'][1]:                                   # no kappa comparison near its threshold
+            assert rec is None or rec[0] * kf == 0 or abs(rec[1] - rec[0] * kf) > 1e-6 * rec[0] * kf
+
+
 # ---- 4. mask_pyramid -----------------------------------------------------------------------------------------
 def test_mask_pyramid_on_odd_shapes_against_hand_written_arrays():
     a = lambda rows: np.array([[ch == '1' for ch in r] for r in rows])

@@ -190,6 +190,7 @@ COUNTS = {
     'smallA11_3_9': (0, 0, 0, 0), 'smallA23_5_7': (0, 0, 18, 13), 'smallA11_5_7': (0, 0, 0, 0),
     'edge_neartie36': (0, 320, 397, 395), 'edge_constA': (400, 400, 397, 397), 'edge_tiny': (0, 0, 397, 307),
     'edge_offset': (0, 400, 393, 393), 'edge_x64edge': (0, 0, 395, 300), 'edge_bigA': (0, 0, 191, 133),
+    'edge_bigA_3_9': (0, 0, 191, 147),
     'x1000': (0, 0, 392, 300), 'pairs2': (0, 0, 141, 100), 'wide45_v0': (0, 0, 403, 314), 'wide45_v1': (0, 0, 404, 336),
     'wide45_v2': (0, 0, 404, 371), 'wide45_v3': (0, 0, 396, 390), 'wide70_v0': (0, 0, 1188, 894), 'wide70_v1': (0, 0, 1185, 937),
 }
@@ -197,6 +198,22 @@ COUNTS = {
 
 def test_every_gpu_case_is_counted():
     assert sorted(COUNTS) == sorted(WI.CASES)
+
+
+def test_big_db_reaches_the_row_kernels_second_grid_trip():
+    """edge_bigA_3_9: k_nbhd_rows runs at most 4,096 workgroups of 256 threads, and this DB has 102,344 elements
+    more; the restatement takes final sources among the rows those elements belong to, so a DB whose tail was not
+    written cannot give its result"""
+    z, e = WI.make('edge_bigA_3_9'), WI.expected('edge_bigA_3_9')
+    a_h, a_w = z['A_pyr'][1].shape[:2]
+    D, rows = WI.width(*z['win'], 1), a_h * a_w
+    assert z['L'] == 2 and z['win'] == (3, 9) and D == 139 and rows == 8280
+    assert WI.ROWS_GRID == 1048576 and rows * D == 1150920 > WI.ROWS_GRID and rows * D - WI.ROWS_GRID == 102344
+    assert WI.BIG_CUT == WI.ROWS_GRID // D == 7543
+    assert -(-rows // 32) == 259                                   # bigA's DB tiles
+    src = (a_h * e['im'][1] + e['s'][1][:, 0]) * a_w + e['s'][1][:, 1]
+    assert len(src) == 192 and int((src >= WI.BIG_CUT).sum()) == 5              # final source rows in the second trip
+    assert sum(1 for x in e['log'] if x[0] >= WI.BIG_CUT) == 12    # and the NN rows there, before the kappa rule
 
 
 @pytest.mark.parametrize('name', sorted(WI.CASES))
@@ -220,10 +237,10 @@ def test_gpu_case_is_what_it_claims(name):
     T, mmax, tiles = WI.step_shape(h, w, n_lg // 2)
     geo = (-(-rows // 32), rows % 32, T, mmax)
     want = {'size': (15, 27, 20 + (n_lg // 2 + 1) * 15, min(16, -(-20 // (n_lg // 2 + 1)))), 'edge_bigA': (259, 24, 60, 4),
-            'wide45': (15, 27, 85, 9), 'wide70': (15, 27, 134, 17), 'pairs2': (8, 16, 53, 4)}
-    for key, g in want.items():
-        if name.startswith(key):
-            assert geo == g, geo
+            'edge_bigA_3_9': (259, 24, 71, 4), 'wide45': (15, 27, 85, 9), 'wide70': (15, 27, 134, 17), 'pairs2': (8, 16, 53, 4)}
+    keys = [key for key in want if name.startswith(key)]
+    if keys:
+        assert geo == want[max(keys, key=len)], geo                # (the longest prefix: edge_bigA_3_9 has p_l = 4)
     if name.startswith('wide45'):
         assert WI.step_shape(h, w, 4, 32)[1] * 32 == 288           # 9 query tiles: three blocks of KH 84's three
         assert WI.width(3, 9, 1) == 139

@@ -180,6 +180,11 @@ for _w in BORDER_WIN:
     CASES['smallA11_%d_%d' % _w] = (lambda w: lambda: rand_case(341, *w, geo=dict(a_hw=(1, 1), b_hw=(5, 4), L=2), n_ap=3))(_w)
 for _n in EDGE_CASES:
     CASES['edge_' + _n] = (lambda n: lambda: sized(AI.make(n), 3, 7))(_n)
+# bigA at (3, 9): D = 139, so the 8,280-row DB has 1,150,920 elements and k_nbhd_rows' 4,096 x 256 grid takes a
+# second trip for the rows from BIG_CUT on (run after another call on the same context: test_gpu_windows.py)
+CASES['edge_bigA_3_9'] = lambda: sized(AI.make('bigA'), 3, 9)
+ROWS_GRID = 4096 * 256                                                   # ia_launch_nbhd_rows: workgroups x threads
+BIG_CUT = ROWS_GRID // 139                                               # the first DB row with an element past the grid
 CASES['x1000'] = lambda: rand_case(350, 3, 7, f=lambda x: 1000 * x)      # far outside the default path's +-64 gate
 CASES['pairs2'] = lambda: sized(PI._rand_pairs(351, 2, geo=dict(a_hw=(12, 10), b_hw=(11, 13), L=2)), 3, 7)
 WIDE_K = AI.WIDE_K
